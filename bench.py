@@ -9,14 +9,17 @@ learned degree k -> all-pairs Gumbel-perturbed scores + per-row top-64 -> smooth
 relu(A (x Wc)), then the full backward with a ones cotangent (all DGG parameters + conv weight; the input features are
 data, as in the reference's training loop, unless --x-grad).  Inputs are resident in HBM before the timed region; every
 step draws fresh noise (seed cycled over NGRAPH values).
-W warm-up steps, then `--repeats` windows of exactly K steps, each bracketed by barrier + synchronize (max over ranks);
-`value` / `ms_per_step` come from the median window.
+W warm-up steps, then ONE window of exactly K timed steps (or `--repeats` windows of K steps), bracketed by barrier + synchronize
+(max over ranks); `value` / `ms_per_step` come from the (median) window.
 One GPU: N = 100 000 (the BASELINE.json metric config).  Several GPUs (torchrun, one rank per GPU, RCCL): BASELINE.json
 configs[3], ONE graph of 500 000 nodes node-range sharded (strong scaling); --weak: 100 000 rows per GPU.
 
-Prints ONE JSON line (rank 0), at most LINE_LIMIT bytes: the driver's fields, `roofline` (dominant kernel), `cpu_baseline`, `repeats` and a
-compact `configs` map ({ms_per_step, value, frac} per secondary BASELINE config).  The full result -- `kernels`, `variants` (symmetric /
-unperturbed / hash noise, latent 128, x-grad), `data_regimes`, per-config detail -- goes to gpurun_out/bench_detail.json and to stderr.
+Prints ONE JSON line (rank 0), at most LINE_LIMIT bytes: the driver's fields, `config` and `repeats`.  --dump-outputs DIR writes what the
+last timed step returned (the layer output Z and every parameter gradient) as DIR/<name>.npy.
+--full adds everything beyond the headline figure: an eager window, as many windows as fill MIN_TIMED_S (unless --repeats), `roofline`
+(dominant kernel), `cpu_baseline`, a compact `configs` map ({ms_per_step, value, frac} per secondary BASELINE config); the full result --
+`kernels`, `variants` (symmetric / unperturbed / hash noise, latent 128, x-grad), `data_regimes`, per-config detail -- goes to the detail
+file (DETAIL_PATH) and to stderr.
 """
 import argparse
 import copy
@@ -742,6 +745,31 @@ def emit_json(obj):
         os.write(_JSON_FD, line)
 
 
+DUMP_LIMIT = 60_000_000    # bytes: all arrays of --dump-outputs together (below 64 MB, headers included)
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: the last timed step's output Z and gradients as <path>/Z.npy, <path>/grad_<name>.npy (float32).  If they do not
+    fit in DUMP_LIMIT, the per-node arrays (Z, and the feature gradient with --x-grad) are cut to one fixed sample of rows (seed 0,
+    ascending), whose row numbers go to <path>/sample_rows.npy (float64)."""
+    Z, grads = last
+    arrs = {"Z": Z.detach().float().cpu().numpy()}
+    arrs.update({"grad_" + k_: v.detach().float().cpu().numpy() for k_, v in sorted(grads.items())})
+    total = sum(v.nbytes for v in arrs.values())
+    if total > DUMP_LIMIT:
+        nrow = arrs["Z"].shape[0]
+        per_node = [k_ for k_, v in arrs.items() if v.ndim == 2 and v.shape[0] == nrow]
+        fixed = total - sum(arrs[k_].nbytes for k_ in per_node)
+        n = (DUMP_LIMIT - fixed) // (sum(arrs[k_].shape[1] * 4 for k_ in per_node) + 8)
+        rows = np.sort(np.random.default_rng(0).choice(nrow, size=n, replace=False))
+        for k_ in per_node:
+            arrs[k_] = arrs[k_][rows]
+        arrs["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k_, v in arrs.items():
+        np.save(os.path.join(path, k_ + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=["synthetic", "synthetic-module", "pubmed", "ppi"], default="synthetic",
@@ -763,15 +791,20 @@ def main():
     ap.add_argument("--nodes", type=int, default=0, help="node count: total (one GPU, or several with strong scaling) or per GPU (--weak); "
                                                           "0 = 100 000 on one GPU, 500 000 in total on several (BASELINE.json configs[3])")
     ap.add_argument("--weak", action="store_true", help="multi-GPU: --nodes (default 100 000) rows PER GPU of a (nodes x GPUs)-node graph")
-    ap.add_argument("--repeats", type=int, default=0, help="timed windows of --steps steps each; value = median window; 0 = as many "
-                                                            "as make the timed region last >= 3 s (at least 11)")
+    ap.add_argument("--repeats", type=int, default=0, help="timed windows of --steps steps each; value = median window; 0 = one window, "
+                                                            "with --full as many as make the timed region last >= 3 s (at least 11)")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: besides the headline figure, measure everything else -- eager window, per-kernel roofline, "
+                         "data regimes, variants, the other BASELINE.json configs, CPU baselines (the options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: write what the last timed step returned (Z and every parameter gradient) as DIR/<name>.npy")
     ap.add_argument("--no-variants", dest="variants", action="store_false",
-                    help="skip the symmetric / unperturbed / hash / latent-128 / x-grad variants of the step (one GPU only)")
+                    help="--full: skip the symmetric / unperturbed / hash / latent-128 / x-grad variants of the step (one GPU only)")
     ap.add_argument("--no-configs", dest="configs", action="store_false",
-                    help="skip the compact lines of the other BASELINE.json configs (Pubmed shape, PPI bf16, N = 500 000 on one GPU) "
-                         "that the default run appends under `configs`")
+                    help="--full: skip the compact lines of the other BASELINE.json configs (Pubmed shape, PPI bf16, N = 500 000 on one GPU) "
+                         "that the run appends under `configs`")
     ap.add_argument("--no-cpu-dense", dest="cpu_dense", action="store_false",
-                    help="skip the dense reference-shaped CPU formulation at N = 2 708 / 4 000 (BASELINE.md section 3)")
+                    help="--full: skip the dense reference-shaped CPU formulation at N = 2 708 / 4 000 (BASELINE.md section 3)")
     ap.add_argument("--prior", default="24,40", help="synthetic workload: prior degrees lo,hi (uniform); 24,40 = SURVEY 8(d) (k ~ 32); 100,164: k ~ 128")
     ap.add_argument("--feat", type=int, default=128)
     ap.add_argument("--latent", type=int, default=64)
@@ -803,6 +836,8 @@ def main():
     ap.add_argument("--cpu-rows", type=int, default=0,
                     help="row sample of the cpu_baseline leg: 0 = auto (64 rows per host core, ~10-20 s), <0 = skip")
     a = ap.parse_args()
+    if a.dump_outputs and a.workload != "synthetic":
+        ap.error("--dump-outputs is implemented for the default (synthetic) workload")
     isolate_stdout()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -908,6 +943,7 @@ class SyntheticRun:
         if self.cot is None or self.cot.shape != Z.shape:
             self.cot = torch.ones_like(Z)                            # the cotangent is an INPUT of the backward: resident, not refilled
         self.grads = self.layer.backward(self.cot, self.x_local, self.P)
+        self.Z = Z
         return self.grads
 
 
@@ -917,10 +953,11 @@ NGRAPH = 4      # captured hipGraphs, one per noise seed: consecutive steps see 
 
 def time_windows(run, a, world, force, dev, use_graph, repeats):
     """W untimed warm-up steps, then windows of EXACTLY a.steps steps, each bracketed by barrier + synchronize; returns
-    (per-window seconds, max over ranks), whether hipGraphs were used, and the per-step time of one EAGER window.
+    (per-window seconds, max over ranks), whether hipGraphs were used, the per-step time of one EAGER window (--full only, else
+    None) and the (Z, gradients) of the last timed step.
     Noise: a fresh realisation every step -- device-resident seed advanced inside the step (ONE captured graph), or, for the
-    generators that take the seed by value, NGRAPH captured graphs cycled.  `repeats` <= 0: as many windows as make the timed
-    region last >= MIN_TIMED_S seconds (so that the driver's GPU-busy sampler sees it), at least 11."""
+    generators that take the seed by value, NGRAPH captured graphs cycled.  `repeats` <= 0: one window; with --full as many windows
+    as make the timed region last >= MIN_TIMED_S seconds (so that the driver's GPU-busy sampler sees it), at least 11."""
     coll = world > 1 or force
     ngraph = 1 if getattr(run, "seed_dev", None) is not None else NGRAPH
     for s_ in range(max(a.warmup, 1)):
@@ -938,36 +975,39 @@ def time_windows(run, a, world, force, dev, use_graph, repeats):
             dist.barrier()
         return time.perf_counter() - t0
 
-    eager_s = window(lambda s_: run.step(s_ % NGRAPH))              # one eager window (also the estimate for the window count)
-    graphs = None
+    full = a.full
+    eager_s = window(lambda s_: run.step(s_ % NGRAPH)) if full else None     # one eager window (also the estimate for the window count)
+    graphs, outs = None, None
     if use_graph:
         try:
             torch.cuda.synchronize()
-            graphs = []
+            graphs, outs = [], []
             for s_ in range(ngraph):
                 gph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gph):
                     run.step(s_)
                 graphs.append(gph)
-            for gph in graphs:
-                gph.replay()
+                outs.append((run.Z, run.grads))                       # (the captured step's output tensors, rewritten by each replay)
+            for s_ in range(len(graphs) if full else max(a.warmup, len(graphs))):    # (plain run: the W warm-up steps on the timed path too)
+                graphs[s_ % len(graphs)].replay()
             torch.cuda.synchronize()
         except Exception as e:  # noqa: BLE001
             print(f"hipGraph capture failed ({e!r}); timing eager launches", file=sys.stderr)
             graphs = None
     launch = (lambda s_: graphs[s_ % ngraph].replay()) if graphs is not None else (lambda s_: run.step(s_ % NGRAPH))
-    first = window(launch)
-    est = torch.tensor([first], device=dev, dtype=torch.float64)
-    if coll:
-        dist.all_reduce(est, op=dist.ReduceOp.MAX)
-    if repeats <= 0:
+    if repeats <= 0 and full:
+        first = window(launch)
+        est = torch.tensor([first], device=dev, dtype=torch.float64)
+        if coll:
+            dist.all_reduce(est, op=dist.ReduceOp.MAX)
         repeats = int(min(max(11, np.ceil(MIN_TIMED_S / max(float(est.item()), 1e-6))), 400))
-    times = [window(launch) for _ in range(repeats)]
-    tm = torch.tensor(times + [eager_s], device=dev, dtype=torch.float64)
+    times = [window(launch) for _ in range(max(repeats, 1))]
+    last = outs[(a.steps - 1) % ngraph] if graphs is not None else (run.Z, run.grads)
+    tm = torch.tensor(times + ([eager_s] if full else []), device=dev, dtype=torch.float64)
     if coll:
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
     tm = [float(v) for v in tm.tolist()]
-    return tm[:-1], graphs is not None, tm[-1] / a.steps
+    return tm[:len(times)], graphs is not None, (tm[-1] / a.steps if full else None), last
 
 
 def cpu_dense_formulation(sizes, threads):
@@ -1012,7 +1052,7 @@ def wide_rows_config(a, dev, prior, N=100_000, noise_mode=None):
     if noise_mode is not None:
         b.steps, b.repeats = 5, 3
     run = SyntheticRun(b, dev, 1, 0, False, N, a.feat, a.latent, ops.NOISE_RANKED if noise_mode is None else noise_mode, prior=prior)
-    times, graphed, eager_T = time_windows(run, b, 1, False, dev, a.hipgraph, b.repeats)
+    times, graphed, eager_T, _ = time_windows(run, b, 1, False, dev, a.hipgraph, b.repeats)
     T = float(np.median(times)) / b.steps
     run.layer.check_wide()
     sv = run.layer.saved
@@ -1168,7 +1208,7 @@ def bench_synthetic(a, dev, world, rank, force):
     # capture on the one GPU there is (DGG_BENCH_GRAPH_DIST=0 times it eagerly).  Several ranks: eager unless DGG_BENCH_GRAPH_DIST=1.
     gd = os.environ.get("DGG_BENCH_GRAPH_DIST")
     use_graph = a.hipgraph and ((world == 1 and gd != "0") if (world == 1 and force) else (world == 1 or gd == "1"))
-    times, graphed, eager_T = time_windows(run, a, world, force, dev, use_graph, a.repeats)
+    times, graphed, eager_T, last = time_windows(run, a, world, force, dev, use_graph, a.repeats)
     T = float(np.median(times)) / a.steps
     layer, P, r0, r1 = run.layer, run.P, run.r0, run.r1
     ksum = layer.saved["k"].sum().reshape(1).double()
@@ -1183,6 +1223,45 @@ def bench_synthetic(a, dev, world, rank, force):
     if lay is not None:
         layer.check_wide()                                        # (a captured step's fixed chunk capacity held every row)
     assert all(torch.isfinite(v).all() for v in run.grads.values())
+    coll = world > 1 or force
+    rows_loc = r1 - r0
+    out = {
+        "metric": METRIC, "value": Nval * kmean / T, "unit": "edges/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": T * 1e3, "higher_is_better": True,
+        "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "repeats": {"windows": len(times), "steps_per_window": a.steps, "value_from": "median window",
+                    "window_ms_per_step_min_median_max": [float(np.min(times)) / a.steps * 1e3, float(np.median(times)) / a.steps * 1e3,
+                                                           float(np.max(times)) / a.steps * 1e3],
+                    "timed_seconds_total": float(sum(times)),
+                    "noise": "fresh seed every step: device-resident seed advanced inside the captured step (one hipGraph)"
+                             if getattr(run, "seed_dev", None) is not None else f"{NGRAPH} captured graphs with different seeds, cycled"},
+        "config": {"workload": f"synthetic all-pairs DGG N={N} d={d} h={h} k~{kmean:.1f} K=64, u-v-dist/x/"
+                               f"k_times_edge_prob, Gumbel(0,0.3) perturbation, + normalize + GCNConv({d},64), fwd+bwd",
+                   "nodes": N, "feat": d, "latent": h, "ell_width": 64, "pairs_per_s": N * float(N) / T,
+                   "x_grad": a.x_grad, "topk_algo": a.algo, "noise": a.noise, "hipgraph": graphed,
+                   "hipgraph_note": None if graphed or not coll else "steps with collectives are launched eagerly (set "
+                                    "DGG_BENCH_GRAPH_DIST=1 to try capturing the RCCL calls)",
+                   "parallelism": f"row-shard x{world}" if not emu else f"DIAGNOSTIC: compute of rank {run.erank} of {emu}, no collectives",
+                   "rows_per_rank": rows_loc,
+                   "feature_exchange": ("single GPU" if not coll else
+                                        "hybrid: features replicated at load, every rank projects xp of all rows and H of its own rows; per step: "
+                                        "async all-gather of H (N*F*4 B, behind k-net + search + partition), all-gather row sums, async "
+                                        "reduce-scatter of the partial dH (behind the score backward), all-reduce da + weight gradients"
+                                        if (run.x_full is not None and run.layer.hybrid) else
+                                        "features replicated at load, every rank projects all rows; per-step collectives: all-gather row sums, "
+                                        "all-reduce da + weight gradients" if run.x_full is not None else
+                                        "per step: all-gather [xp | H] (projections of the own rows), all-gather row sums, all-reduce da, "
+                                        "reduce-scatter [dxp | dH], all-reduce weight gradients")},
+    }
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
+    if not a.full:
+        if rank == 0:
+            emit_json(out)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+    out["repeats"]["eager_ms_per_step"] = eager_T * 1e3
 
     # Per-kernel roofline figures: durations taken INSIDE running steps.  dgg_amd.ops records a pair of events on the launch
     # stream around the C-ABI call of each gather kernel (ops.PROBE); PROBE_STEPS eager steps are run for that after the timed
@@ -1198,7 +1277,6 @@ def bench_synthetic(a, dev, world, rank, force):
     if "edge_bwd" not in tk:                                      # two-stream step: the score backward is probed as its two launches
         tk["edge_bwd"] = tk["edge_bwd_rows"] + tk["edge_bwd_node"]
     sv = layer.saved
-    rows_loc = r1 - r0
     F = int(sv["H"].shape[1])                                     # width of the aggregated (projected) rows
     active = float((sv["w"] != 0).sum().item())                   # edges with a non-saturated ramp (~ k + 8.5 per row)
     kept = float((sv["idx"] >= 0).sum().item())                   # ranks kept by k_limit (~ k + 9.5 per row)
@@ -1387,34 +1465,7 @@ def bench_synthetic(a, dev, world, rank, force):
                 variants[name] = {"error": repr(e)}
 
     if rank == 0:
-        coll = world > 1 or force
-        out = {
-            "metric": METRIC, "value": Nval * kmean / T, "unit": "edges/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": T * 1e3, "higher_is_better": True,
-            "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "repeats": {"windows": len(times), "steps_per_window": a.steps, "value_from": "median window",
-                        "window_ms_per_step_min_median_max": [float(np.min(times)) / a.steps * 1e3, float(np.median(times)) / a.steps * 1e3,
-                                                               float(np.max(times)) / a.steps * 1e3],
-                        "timed_seconds_total": float(sum(times)), "eager_ms_per_step": eager_T * 1e3,
-                        "noise": "fresh seed every step: device-resident seed advanced inside the captured step (one hipGraph)"
-                                 if getattr(run, "seed_dev", None) is not None else f"{NGRAPH} captured graphs with different seeds, cycled"},
-            "config": {"workload": f"synthetic all-pairs DGG N={N} d={d} h={h} k~{kmean:.1f} K=64, u-v-dist/x/"
-                                   f"k_times_edge_prob, Gumbel(0,0.3) perturbation, + normalize + GCNConv({d},64), fwd+bwd",
-                       "nodes": N, "feat": d, "latent": h, "ell_width": 64, "pairs_per_s": N * float(N) / T,
-                       "x_grad": a.x_grad, "topk_algo": a.algo, "noise": a.noise, "hipgraph": graphed,
-                       "hipgraph_note": None if graphed or not coll else "steps with collectives are launched eagerly (set "
-                                        "DGG_BENCH_GRAPH_DIST=1 to try capturing the RCCL calls)",
-                       "parallelism": f"row-shard x{world}" if not emu else f"DIAGNOSTIC: compute of rank {run.erank} of {emu}, no collectives",
-                       "rows_per_rank": rows_loc,
-                       "feature_exchange": ("single GPU" if not coll else
-                                            "hybrid: features replicated at load, every rank projects xp of all rows and H of its own rows; per step: "
-                                            "async all-gather of H (N*F*4 B, behind k-net + search + partition), all-gather row sums, async "
-                                            "reduce-scatter of the partial dH (behind the score backward), all-reduce da + weight gradients"
-                                            if (run.x_full is not None and run.layer.hybrid) else
-                                            "features replicated at load, every rank projects all rows; per-step collectives: all-gather row sums, "
-                                            "all-reduce da + weight gradients" if run.x_full is not None else
-                                            "per step: all-gather [xp | H] (projections of the own rows), all-gather row sums, all-reduce da, "
-                                            "reduce-scatter [dxp | dH], all-reduce weight gradients")},
+        out.update({
             # dominant kernel BY TIME of the step (an O(N*K) gather kernel since the pair stage became O(N*150))
             "roofline": {"bound": "hbm", "kernel": dom, "rocprof_kernel": ROCPROF_NAME.get(dom), "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": kern[dom]["GBps"] / HBM_PEAK_GBPS, "traffic": traffic.get(dom) if lay is None else None,
@@ -1453,7 +1504,7 @@ def bench_synthetic(a, dev, world, rank, force):
                                    "`symmetric` / `unperturbed` / `hash_asymmetric` variants"},
             "data_regimes": regimes,
             "variants": variants,
-        }
+        })
         # ---- the other BASELINE.json configs, compact, in the SAME line (the driver runs only this default command): configs[1] Pubmed
         # shape through the drop-in modules, configs[4] PPI shape with bf16 layer products, configs[3]'s 500 000-node graph on one GPU
         if world == 1 and not force and not emu and a.configs and a.variants and N == 100_000:

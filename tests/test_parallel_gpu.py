@@ -137,7 +137,7 @@ def test_bench_prints_exactly_one_json_line_with_rccl_initialised():
     import subprocess
     env = dict(os.environ, DGG_FORCE_COLLECTIVES="1", MASTER_PORT="29575")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", "20000", "--steps", "3", "--warmup", "1",
-                        "--cpu-rows", "-1"], env=env, capture_output=True, text=True, timeout=600)
+                        "--cpu-rows", "-1", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-1000:]

@@ -3,9 +3,9 @@
 profiles/r02_traffic.json: FABRIC bytes per launch (L2 -> fabric requests; Infinity-Cache hits are counted, the guide's
 "HBM" section) for the kernels bench.py reports, stamped with the shape they were measured on.
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --repeats 1 --cpu-rows -1 --no-hipgraph --no-variants
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 3 --warmup 1 --repeats 1 --cpu-rows -1 --no-hipgraph --no-variants
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r02_traffic.json [nodes feat latent]
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_fetch -- python3 bench.py --full --steps 3 --warmup 1 --repeats 1 --cpu-rows -1 --no-hipgraph --no-variants
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_write -- python3 bench.py --full --steps 3 --warmup 1 --repeats 1 --cpu-rows -1 --no-hipgraph --no-variants
+    python tools/pmc_traffic.py /tmp/pmc_fetch /tmp/pmc_write profiles/r02_traffic.json [nodes feat latent]
 
 gfx950 corrections: FETCH_SIZE counts 64 B per 128-B request -> doubled; both counters are in KiB."""
 import csv

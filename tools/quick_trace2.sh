@@ -5,7 +5,7 @@ R="${GRAFT_REPO_ROOT:?run on the GPU box through gpurun}"
 name=$1; shift
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/qt_$name
-rocprofv3 --kernel-trace --stats -d /tmp/qt_$name -o h -- python3 "$R/bench.py" --steps 20 --warmup 5 --repeats 3 --cpu-rows -1 --no-variants --no-configs "$@" > /tmp/qt_$name.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d /tmp/qt_$name -o h -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --repeats 3 --cpu-rows -1 --no-variants --no-configs "$@" > /tmp/qt_$name.json 2>/dev/null
 cd "$R"
 python3 tools/kernel_stats.py /tmp/qt_$name/h_results.db gpurun_out/${name}_kernel_stats.csv --skip-first 8 > /dev/null
 python3 - <<PY

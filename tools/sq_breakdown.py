@@ -2,7 +2,7 @@
 """Where the wavefront cycles of each kernel go, from one rocprofv3 PMC pass over the SQ block
 
     rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \\
-              --output-format csv -d DIR -- python3 bench.py --steps 3 --warmup 1 --repeats 1 --cpu-rows -1 --no-hipgraph --no-variants
+              --output-format csv -d DIR -- python3 bench.py --full --steps 3 --warmup 1 --repeats 1 --cpu-rows -1 --no-hipgraph --no-variants
     python tools/sq_breakdown.py DIR out.csv
 
 MI355X_MICROARCH.md ("rocprofv3 PMC slots"): SQ_WAVE_CYCLES ~ SQ_WAIT_ANY (parked on s_waitcnt / barrier) + SQ_WAIT_INST_ANY (issue
