@@ -4,6 +4,7 @@
 Public surface mirrors the reference's modules:
     dgg_amd.dgm.{DGG_LearnableK_debug, DGG, LearnableKEncoder}               (reference dgm.py)
     dgg_amd.model.{GCNConv, GraphConvolution, DenseGraphConvolution, GCN_DGG, GCN_DGG_00, GCNII_DGG, GCNIIppi_DGG}  (model.py)
+    dgg_amd.distributed.{ShardedGCN_DGG, global_nll_loss}                    (GCN_DGG row-sharded across GPUs)
 plus the containers `AllPairs` / `EllAdjacency` / `CsrAdjacency` and the raw kernel wrappers in `dgg_amd.ops`.
 """
 from . import _lib, ops  # noqa: F401
@@ -13,3 +14,4 @@ from .dgm import (DGG, DGG_Ablations, DGG_LearnableK_debug, DGG_LearnableK_SDD, 
 from .model import (DenseGraphConv, DenseGraphConvolution, GAT_DGG_00, GAT_DGG_Ablations, GATConv_DGG, GCN_DGG, GCN_DGG_00,  # noqa: F401
                     GCN_DGG_Ablations, GCNConv, GCNII_DGG, GCNIIppi_DGG,
                     GraphConvolution, SAGE_DGG, SAGE_DGG_00)
+from .distributed import ShardedGCN_DGG, global_nll_loss  # noqa: F401

@@ -366,6 +366,11 @@ class _FusedDGGConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, deg, layer, *params):
         x, params, ctx.d_orig = _pad_features(x, params, layer.PARAM_KEYS)
+        if layer.x_full is not None:
+            # replicated features (dgg_amd.distributed): x holds every node, projected whole for the scoring side; the rest of the
+            # step reads the layer's own rows
+            layer.x_full, x = x, x[layer.r0:layer.r1]
+        ctx.x_full = layer.x_full
         P = dict(zip(layer.PARAM_KEYS, params))
         # (layer.want_backward was set by forward_conv BEFORE .apply(): grad mode is always off in here, and ctx.needs_input_grad says
         #  (True, ...) under torch.no_grad() too)
@@ -386,6 +391,7 @@ class _FusedDGGConvFn(torch.autograd.Function):
         layer = ctx.layer
         P = dict(zip(layer.PARAM_KEYS, params))
         layer.saved, layer._fwd_gen = ctx.state, ctx.state["gen"]       # (another forward of the same module may have run since)
+        layer.x_full = ctx.x_full
         layer.x_grad = bool(ctx.needs_input_grad[0])
         if dZ is None:
             dZ = torch.zeros_like(ctx.state["Z"])
@@ -633,6 +639,11 @@ class DGG_LearnableK_debug(nn.Module):
         The steps: _fused_outside (configurations the node does not cover) -> candidates -> _fused_scorer (edge-MLP terms) ->
         _fused_configure (noise generator, what rows wider than 64 ranks do, flags) -> the node -> _fused_result (what the forward's
         learned degrees decide after the fact, the returned adjacencies)."""
+        return self._forward_conv(x, in_adj, conv_weight, want_norm)
+
+    def _forward_conv(self, x, in_adj, conv_weight, want_norm, engine=None):
+        """forward_conv on the module's own one-GPU engine (engine None) or on the caller's: a ShardedDGGConv of a row shard on replicated
+        features (dgg_amd.distributed.ShardedGCN_DGG) takes the same configuration and the same node, and gets back its own rows"""
         from .parallel import ShardedDGGConv
         why = self._fused_outside(x, in_adj, conv_weight)
         if why is not None:
@@ -654,8 +665,8 @@ class DGG_LearnableK_debug(nn.Module):
             if wide_state is True:                            # (known before any kernel runs: this graph takes the CSR form -- no discarded forward)
                 return self._fused_fallback("rows wider than the list with learned degrees beyond it (CSR form)")
         mlp, sc_static = self._fused_scorer(in_adj) if mlp_mode else (None, None)
-        layer = self.__dict__.get("_fused_layer")
-        if layer is None or layer.N != N:
+        layer = self.__dict__.get("_fused_layer") if engine is None else engine
+        if engine is None and (layer is None or layer.N != N):
             layer = self.__dict__["_fused_layer"] = ShardedDGGConv(ops, N, K=64, t=ops.T_DIST)
         noise_mode, chunk_active = self._fused_configure(layer, x, cand, wide_state, mlp_mode)
         kn = self.k_net

@@ -1,0 +1,241 @@
+"""Row-sharded training of GCN_DGG across the GPUs of one node through the nn.Module API (one process per GPU).
+
+    net = ShardedGCN_DGG(model)                     # shares model's parameters, state_dict and optimiser groups
+    logp, adj, _ = net(x, AllPairs(deg))            # x [N, d] and deg [N] replicated; logp = this rank's rows net.rows
+    loss = global_nll_loss(logp, labels, idx_train, net.rows)
+    loss.backward()                                 # every rank now holds the full-graph gradient of every parameter
+
+Layer 1 (generator + normalize_adj + GCNConv) is the fused node of DGG_LearnableK_debug.forward_conv over a row shard of
+dgg_amd.parallel.ShardedDGGConv on replicated features with the hybrid exchange; layer 2 is relu(Â_local (x1 W2)) over all N columns
+with x1 W2 (or x1) all-gathered and its cotangent reduce-scattered (_ShardedConvFn).  Both layers sum the replicated weight gradients
+over the ranks inside their autograd nodes, so identical optimisers keep the ranks' parameters bit-identical.
+
+The reference has no distributed code; its loss is F.nll_loss(out[idx], labels[idx])
+(train_small_graphs.py:226), which global_nll_loss splits over the ranks.
+"""
+import torch
+import torch.distributed as dist
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .adjacency import AllPairs
+from .dgm import _capturing
+from .model import GCN_DGG
+from .parallel import ShardedDGGConv, _all_gather_rows, shard_bounds
+
+
+def _world(group):
+    return (dist.get_world_size(group), dist.get_rank(group)) if dist.is_initialized() else (1, 0)
+
+
+def _reduce_scatter_rows(t, eng):
+    """[N, c] partial sums on every rank -> the rank's own rows [r1 - r0, c], summed over the ranks (fresh buffers: the result is an
+    autograd gradient)"""
+    pad = eng.world * eng.per - eng.N
+    src = torch.cat([t, t.new_zeros((pad, t.shape[1]))]) if pad else t.contiguous()
+    out = t.new_empty((eng.per, t.shape[1]))
+    dist.reduce_scatter_tensor(out, src, group=eng.group)
+    return out[:eng.r1 - eng.r0]
+
+
+class _ShardedConvFn(torch.autograd.Function):
+    """GCN_DGG's second GCNConv on a row shard: relu(Â_local (x1 W)) with Â_local [rows, N] the normalised adjacency of layer 1's rows
+    (global columns).  The order follows GCNConv.forward: x1 W first when out <= in and out is a width of the per-destination backward,
+    (Â x1) W otherwise; the all-gathered operand is the narrower one.  The kernels are those GCNConv runs on one GPU (spmm_fwd,
+    conv_bwd_cols_p on layer 1's payload partition, linear_fwd / linear_bwd); at one rank without collectives the bits are the same."""
+
+    @staticmethod
+    def forward(ctx, x1, ahat, W, eng, idx, layout, partp):
+        fin, fout = W.shape
+        gather = (lambda t_: _all_gather_rows(t_, eng.N, eng.per, eng.group)) if eng.coll else (lambda t_: t_)
+        ctx.eng, ctx.idx, ctx.layout, ctx.partp = eng, idx, layout, partp
+        ctx.first = fout <= fin and fout in ops.CONV_BWD_WIDTHS
+        if ctx.first:
+            H_loc = ops.linear_fwd(x1, W, None, ops.ACT_NONE, 1)
+            H = gather(H_loc)
+            Y = ops.spmm_fwd(idx, ahat, H, ops.ACT_RELU, layout=layout)
+            ctx.save_for_backward(x1, W, H_loc, H, Y)
+        else:
+            X = gather(x1)
+            AX = ops.spmm_fwd(idx, ahat, X, ops.ACT_NONE, layout=layout)
+            Y = ops.linear_fwd(AX, W, None, ops.ACT_RELU, 1)
+            ctx.save_for_backward(x1, W, X, AX, Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        eng, idx, partp = ctx.eng, ctx.idx, ctx.partp
+        if partp is None:
+            raise RuntimeError("ShardedGCN_DGG: this forward ran without a backward to follow (torch.no_grad() or frozen parameters), "
+                               "so layer 1 did not sort the partition the second layer's backward runs on")
+        dY = dY.contiguous()
+        if ctx.first:
+            x1, W, H_loc, H, Y = ctx.saved_tensors
+            G = ops.act_bwd(Y, dY, ops.ACT_RELU)
+            got = ops.conv_bwd_cols_p(idx, H, G, partp[0], partp[1], zero_dA=True)
+            if got is None:
+                raise RuntimeError("ShardedGCN_DGG: the second layer's shape is outside the per-destination backward (conv_bwd_cols_p)")
+            dA, _, dH, _ = got
+            if eng.coll:
+                dH = _reduce_scatter_rows(dH, eng)
+            dx1, dW, _ = ops.linear_bwd(x1, W, H_loc, dH, ops.ACT_NONE, 1, need_dx=ctx.needs_input_grad[0], need_db=False)
+        else:
+            x1, W, X, AX, Y = ctx.saved_tensors
+            dAX, dW, _ = ops.linear_bwd(AX, W, Y, dY, ops.ACT_RELU, 1, need_dx=True, need_db=False)
+            got = ops.conv_bwd_cols_p(idx, X, dAX.contiguous(), partp[0], partp[1], zero_dA=True)
+            if got is None:
+                raise RuntimeError("ShardedGCN_DGG: the second layer's shape is outside the per-destination backward (conv_bwd_cols_p)")
+            dA, _, dx1, _ = got
+            if eng.coll:
+                dx1 = _reduce_scatter_rows(dx1, eng)
+        if eng.coll:
+            dist.all_reduce(dW, group=eng.group)
+        return dx1, dA, dW, None, None, None, None
+
+
+class ShardedGCN_DGG(nn.Module):
+    """GCN_DGG (reference model.py:1183-1311) on a row shard of the graph: rank r of `group` computes rows [r0, r1) = `.rows`
+    (parallel.shard_bounds) of the log-probabilities against all N columns.
+
+    The wrapper owns no parameters of its own: it holds `model` (whose parameters it broadcasts from the group's first rank when
+    there are several), and `state_dict()` / `load_state_dict()` / `params1` / `params2` are the model's, so checkpoints and the
+    optimiser groups of train_small_graphs.py are unchanged.  forward(x, in_adj) takes the FULL features x [N, d] (data, replicated on
+    every rank) and in_adj = AllPairs(prior degrees of all N nodes); it returns (log_probs of the rank's rows, the DETACHED unnormalised
+    EllAdjacency of those rows with global column indices, None).  After backward() every rank holds the full-graph gradient of every
+    parameter when the loss is global_nll_loss (or any loss whose per-rank parts sum to the whole).
+
+    Every rank must draw the same noise: seed the CPU generator identically on every rank (torch.manual_seed) or call
+    model.dggs[0].set_seed.  The dropout between the layers draws each rank's mask from its own CUDA generator.
+    Outside its coverage the wrapper raises (no silent fall-back): edge-list candidates on several ranks (one rank: the model itself
+    runs them), a writer, configurations the fused layer declines, a hipGraph capture on several ranks, args.dgg_hard_literal,
+    args.dgg_differentiable_adj, args.dgg_wide_rows other than 'auto' / 'chunked', and on several ranks args.dgg_sym_generator = 'auto'
+    (a generator switch decided from one rank's rows)."""
+
+    def __init__(self, model, group=None):
+        super().__init__()
+        if not isinstance(model, GCN_DGG):
+            raise TypeError(f"ShardedGCN_DGG wraps a GCN_DGG, not {type(model).__name__}")
+        self.module = model
+        self.group = group
+        self.world, self.rank = _world(group)
+        self._engine = None
+        self._rows = None
+        if self.world > 1:
+            src = 0 if group is None else dist.get_global_rank(group, 0)
+            with torch.no_grad():
+                for p_ in model.parameters():
+                    dist.broadcast(p_.data, src=src, group=group)
+
+    # --- the model's parameters, checkpoints and optimiser groups ------------------------------------------------------------------
+    def state_dict(self, *args, **kwargs):
+        return self.module.state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        return self.module.load_state_dict(state_dict, strict=strict, assign=assign)
+
+    @property
+    def params1(self):
+        return self.module.params1
+
+    @property
+    def params2(self):
+        return self.module.params2
+
+    @property
+    def rows(self):
+        """(r0, r1): the rows of the graph this rank computes (known from the first forward on)"""
+        if self._rows is None:
+            raise RuntimeError("ShardedGCN_DGG.rows: the node count is known from the first forward on")
+        return self._rows
+
+    # ------------------------------------------------------------------------------------------------------------------------------
+    def _check(self, x, in_adj, writer):
+        m = self.module
+        dgg, a = m.dggs[0], m.dggs[0].args
+        if writer is not None:
+            raise NotImplementedError("ShardedGCN_DGG: a writer (histograms of the whole graph) is not supported on a row shard")
+        if self.world > 1 and not isinstance(in_adj, AllPairs):
+            raise NotImplementedError("ShardedGCN_DGG: edge-list candidates run on one rank (in_adj must be AllPairs(prior_degree) when "
+                                      "the group has several ranks)")
+        if self.world > 1 and _capturing():
+            raise NotImplementedError("ShardedGCN_DGG: a hipGraph capture of a step on several ranks is not supported")
+        if getattr(a, "dgg_hard_literal", False):
+            raise NotImplementedError("ShardedGCN_DGG: args.dgg_hard_literal is not supported")
+        if m.differentiable_adj:
+            raise NotImplementedError("ShardedGCN_DGG: args.dgg_differentiable_adj needs the separate modules (one GPU: the model itself)")
+        if x.requires_grad:
+            raise ValueError("ShardedGCN_DGG: the features are data replicated on every rank; they cannot take a gradient")
+        if not isinstance(in_adj, AllPairs):
+            return
+        if in_adj.prior_degree.shape[0] != x.shape[0]:
+            raise ValueError(f"ShardedGCN_DGG: in_adj carries {in_adj.prior_degree.shape[0]} prior degrees for {x.shape[0]} nodes "
+                             "(both are the whole graph's)")
+        policy = getattr(a, "dgg_wide_rows", "auto")
+        if policy not in ("auto", "chunked"):
+            raise NotImplementedError(f"ShardedGCN_DGG: args.dgg_wide_rows = {policy!r} (rows wider than the list need the chunked form)")
+        if self.world > 1 and getattr(a, "dgg_sym_generator", "ranked") == "auto":
+            raise NotImplementedError("ShardedGCN_DGG: args.dgg_sym_generator = 'auto' switches generators from one rank's rows; "
+                                      "choose 'ranked' or 'hash' on several ranks")
+        why = dgg._fused_outside(x, in_adj, m.conv1.W)
+        if why is not None:
+            raise NotImplementedError(f"ShardedGCN_DGG: the fused layer does not cover this configuration ({why})")
+
+    def forward(self, x, in_adj, noise=True, epoch=None, writer=None):
+        m = self.module
+        self._check(x, in_adj, writer)
+        N = x.shape[0]
+        self._rows = shard_bounds(N, self.world, self.rank)[:2]
+        if not isinstance(in_adj, AllPairs):                 # (one rank: edge-list candidates are the model's own step)
+            return m(x, in_adj, noise=noise, epoch=epoch, writer=writer)
+        eng = self._engine
+        if eng is None or eng.N != N:
+            eng = self._engine = ShardedDGGConv(ops, N, group=self.group, K=64, t=ops.T_DIST, x_full=x, hybrid=True)
+        got = m.dggs[0]._forward_conv(x, in_adj, m.conv1.W, True, engine=eng)
+        if got is None:
+            raise NotImplementedError("ShardedGCN_DGG: this forward left the fused layer's coverage "
+                                      f"({m.dggs[0].__dict__.get('fused_fallback', {})})")
+        z, unnorm, norm = got
+        z = F.dropout(z, training=m.training)
+        out = _ShardedConvFn.apply(z, norm.values(), m.conv2.W, eng, norm.idx, norm.layout, norm.partp)
+        return F.log_softmax(out, dim=-1), unnorm, None
+
+
+_SEL_CACHE = {}
+
+
+def _local_selection(labels, idx, rows, device):
+    """-> (own positions of the rank's share of idx [n], their labels [n], global count).  labels and idx are data: the selection is
+    cached per tensor OBJECT and version (one synchronisation per new pair), as adjacency._cached does for the candidate graph."""
+    import weakref
+    key = (id(labels), id(idx), tuple(rows), str(device))
+    ent = _SEL_CACHE.get(key)
+    if ent is not None and ent[0]() is labels and ent[1]() is idx and ent[2] == (labels._version, idx._version):
+        return ent[3]
+    r0, r1 = rows
+    i_ = idx.to(device)
+    if i_.dtype == torch.bool:
+        own, total = torch.nonzero(i_[r0:r1]).reshape(-1), int(i_.sum())
+    else:
+        i_ = i_.long()
+        own, total = i_[(i_ >= r0) & (i_ < r1)] - r0, int(i_.numel())
+    got = (own, labels.to(device)[own + r0].long(), total)
+    for k_ in [k_ for k_, v in _SEL_CACHE.items() if v[0]() is None or v[1]() is None]:
+        del _SEL_CACHE[k_]
+    _SEL_CACHE[key] = (weakref.ref(labels), weakref.ref(idx), (labels._version, idx._version), got)
+    return got
+
+
+def global_nll_loss(log_probs_local, labels, idx, rows, group=None):
+    """F.nll_loss(out[idx], labels[idx]) of the whole graph (reference train_small_graphs.py:226) from each rank's rows: the rank's
+    share of idx, summed and divided by the GLOBAL count.  The value returned is the whole loss on every rank (one scalar all-reduce);
+    its gradient is the rank's share only -- the collectives inside ShardedGCN_DGG's backward sum the shares.
+    labels [N] (all nodes), idx: indices into the N nodes (duplicates count twice, as in the reference) or a boolean mask [N]."""
+    own, lab, total = _local_selection(labels, idx, rows, log_probs_local.device)
+    part = -log_probs_local[own, lab].sum() / total
+    world, _ = _world(group)
+    if world == 1:
+        return part
+    whole = part.detach().clone()
+    dist.all_reduce(whole, group=group)
+    return whole + (part - part.detach())                     # (the value of the whole, the gradient of the share)

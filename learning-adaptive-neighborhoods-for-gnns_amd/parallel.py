@@ -205,7 +205,17 @@ class ShardedDGGConv:
             "ShardedDGGConv: chunked rows inside a hipGraph capture need a fixed capacity (wide_cap = (chunks, lists))"
         lay = kern.chunk_layout(k, ncols=self.N)
         self.last_layout = (lay.chunks, lay.maxm)
-        if not lay.wide and self.wide_rows == "auto" and not self.force_chunked:
+        chunked = lay.wide or self.force_chunked
+        if self.coll and self.noise_mode == 5:
+            # the ranked symmetric generator has no wide-row form: chunked rows are evaluated under the symmetric per-pair hash
+            # (WIDE_NOISE), and G_ij of one rank must be G_ji of the other -- so every rank takes the generator of the rank that needs
+            # it (one MAX all-reduce of the deciding flags; the readback above has synchronised already)
+            flags = torch.tensor([int(lay.wide), int(self.force_chunked), int(self.sym_hash)], dtype=torch.int32, device=k.device)
+            dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=self.group)
+            wide_any, force_any, sym_hash_any = (bool(v) for v in flags.tolist())
+            chunked = wide_any or force_any
+            self.sym_hash = sym_hash_any
+        if not chunked and self.wide_rows == "auto":
             return None
         return lay
 
