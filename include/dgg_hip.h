@@ -265,6 +265,15 @@ int dgg_edgelist_topk(const float *xp, int64_t N, int h, const int64_t *rowptr, 
 int dgg_edgelist_topk_softk(const float *xp, int64_t N, int h, const int64_t *rowptr, const int32_t *col, float t,
                             int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, const float *k,
                             int mode, int32_t *idx, float *val, float *w, float *rs, int32_t *overflow, void *stream);
+/* Row-shard forms of the edge-list entries (same kernels; the entries above are these with [row0, row1) = [0, N)).  A shard passes
+ * its REBASED CSR slice: rowptr [row1-row0+1] with rowptr[0] = 0 (rowptr_global[row0..row1] - rowptr_global[row0]) and col / p_edge /
+ * per-edge arrays = entries [rowptr_global[row0], rowptr_global[row1]) of the global ones (global column ids).  Per-node arrays (xp, AB,
+ * deg) have global length N; per-row inputs and outputs (k, G, idx, val, eid, w, rs, dval, dex) are the shard's [row1-row0, ...] rows.
+ * The noise is keyed on the GLOBAL pair (row0 + i, j): every rank draws the single process's noise with no coordination. */
+/* dgg_edgelist_topk_softk on rows [row0, row1) (dgm.py:1404-1420, 1613-1614 for the shard's rows) */
+int dgg_edgelist_topk_softk_rows(const float *xp, int64_t N, int h, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                                 float t, int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, const float *k,
+                                 int mode, int32_t *idx, float *val, float *w, float *rs, int32_t *overflow, void *stream);
 
 /* ---- edge-MLP scorers on a candidate edge list (dgm.py:1628-1725: u-v-A_uv, u-v-deg, u-v-deg-dist, edge_conv, A_uv) --
  * The reference evaluates sigmoid(W2 act(W1 [x_u, x_v, extras] + b1) + b2) per edge (edge_encode, dgm.py:1101-1105;
@@ -283,6 +292,11 @@ int dgg_edge_mlp_fwd(const float *AB, const float *xp, int64_t N, int h, int hw,
 int dgg_edgelist_topk_p(const float *p_edge, int64_t N, const int64_t *rowptr, const int32_t *col, int noise_mode,
                         const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx, float *val, int32_t *eid,
                         void *stream);
+/* dgg_edgelist_topk_p on rows [row0, row1) (dgm.py:1211-1229, 1404 for the shard's rows; the shard's rebased CSR slice, see
+ * dgg_edgelist_topk_softk_rows): eid indexes the shard's own per-edge arrays (p_edge, and the ex / a_uv slices the backward reads) */
+int dgg_edgelist_topk_p_rows(const float *p_edge, int64_t N, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                             int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx, float *val,
+                             int32_t *eid, void *stream);
 /* autograd of dgg_edge_mlp_fwd for the selected entries: dval (wrt the stored score) -> dAB [N,2*hw] and
  * dpar [5*hw+1] = [dwdu | dwdv | dwex | db1 | dw2 | db2] (both ACCUMULATED into: caller zeroes), dex [N,K] (nullable,
  * overwritten; gradient wrt the per-edge extra).  ex [E] as written by the forward (nullable when ex_mode was 0). */
@@ -290,6 +304,13 @@ int dgg_edge_mlp_bwd(const float *AB, int64_t N, int hw, const int64_t *rowptr, 
                      const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
                      const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
                      int perturb, float *dAB, float *dpar, float *dex, void *stream);
+/* dgg_edge_mlp_bwd on rows [row0, row1) (autograd of dgm.py:1628-1725 for the shard's rows): AB / dAB [N,2*hw] and deg [N] are every
+ * node's; row i of the block is node row0 + i, whose row side (A_u, deg_u, dA_u) is read / written at u = row0 + i; the neighbour side
+ * is unchanged.  rowptr (CSR-valued block) / idx / eid / val / dval / dex are the shard's rows. */
+int dgg_edge_mlp_bwd_rows(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *idx,
+                          const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
+                          const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
+                          int perturb, float *dAB, float *dpar, float *dex, void *stream);
 /* the same for an ELL block whose payload partition (dgg_partp_build of (idx, w), with its entry -> record map: dgg_partp_has_map(N))
  * is at hand: the neighbour-side sums d B_j WITHOUT float atomics -- every selected entry's term is stored as a row of dz_rec in
  * record order (the records of a destination node are consecutive) and a second kernel adds each node's rows.  w [N,K]: the weights
@@ -299,6 +320,12 @@ int dgg_edge_mlp_bwd_partp(const float *AB, int64_t N, int hw, const int32_t *id
                            const float *w, int K, const float *deg, const float *ex, const float *wdu, const float *wdv, const float *wex,
                            const float *b1, const float *w2, const float *b2, int act, int perturb, const void *partp_ws, int64_t ncols,
                            float *dz_rec, int64_t dz_rows, float *dAB, float *dpar, float *dex, void *stream);
+/* dgg_edge_mlp_bwd_partp on rows [row0, row1), as dgg_edge_mlp_bwd_rows: the partition is the shard's (dgg_partp_build of its
+ * [row1-row0, K] block against ncols = N columns) */
+int dgg_edge_mlp_bwd_partp_rows(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int32_t *idx, const int32_t *eid,
+                                const float *val, const float *dval, const float *w, int K, const float *deg, const float *ex, const float *wdu,
+                                const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act, int perturb,
+                                const void *partp_ws, float *dz_rec, int64_t dz_rows, float *dAB, float *dpar, float *dex, void *stream);
 
 /* ---- CSR-valued adjacency (variable row length) + the `DGG` class "for ICLR" (dgm.py:1730-1815) ---------------------
  * `DGG.forward` keeps every candidate edge (weight rank * (ramp + 1), dgm.py:1804-1807), so its output has the sparsity

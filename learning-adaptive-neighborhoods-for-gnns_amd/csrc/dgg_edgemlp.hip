@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void edge_mlp_fwd_kernel(
 // ---- perturbation + per-row top-K on given edge probabilities: one wavefront per row ----------------------------------
 // key payload = position of the candidate in its row (columns of a row ascend -> same tie order as the column key)
 __global__ __launch_bounds__(256) void edgelist_topk_p_kernel(
-    const float *__restrict__ p_edge, int64_t N, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+    const float *__restrict__ p_edge, int64_t N, int64_t row0, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     int noise_mode, const float *__restrict__ G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *__restrict__ idx,
     float *__restrict__ val, int32_t *__restrict__ eid) {
     const int lane = threadIdx.x & 63;
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void edgelist_topk_p_kernel(
             float v = p_edge[e];
             if (noise_mode != 0) {
                 const int32_t j = col[e];
-                const float g = noise_mode == 1 ? G[i * ldG + j] : pair_noise(s0, s1, (uint32_t)i, (uint32_t)j, sym);
+                const float g = noise_mode == 1 ? G[i * ldG + j] : pair_noise(s0, s1, (uint32_t)(row0 + i), (uint32_t)j, sym);
                 v = c_exp(__fadd_rn(c_log(__fadd_rn(v, 1e-8f)), g));
             }
             key = make_key(v, (int32_t)(e - e0));
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void edge_mlp_colsum(const int *__restrict__ n
 // rows of a persistent workgroup -> LDS -> one atomic per workgroup and element.
 template <int VEC>
 __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
-    const float *__restrict__ AB, int64_t N, int hw, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ idx,
+    const float *__restrict__ AB, int64_t N, int64_t row0, int hw, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ idx,
     const int32_t *__restrict__ eid, const float *__restrict__ val, const float *__restrict__ dval, int K,
     const float *__restrict__ deg,
     const float *__restrict__ ex, const float *__restrict__ wdu, const float *__restrict__ wdv,
@@ -162,10 +162,11 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
     const float b2v = b2[0];
     float g_wdu[VEC] = {}, g_wdv[VEC] = {}, g_wex[VEC] = {}, g_b1[VEC] = {}, g_w2[VEC] = {}, g_b2 = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < N; i += (int64_t)gridDim.x * 4) {
+        const int64_t u = row0 + i;                              // (i: the block's row, u: its node -- the row side of AB / deg / dAB)
         float Ai[VEC], dA[VEC] = {};
 #pragma unroll
-        for (int q = 0; q < VEC; q++) Ai[q] = AB[i * 2 * hw + o0 + q];
-        const float du = deg ? deg[i] : 0.0f;
+        for (int q = 0; q < VEC; q++) Ai[q] = AB[u * 2 * hw + o0 + q];
+        const float du = deg ? deg[u] : 0.0f;
         // entries of the row: ELL [i*K, i*K+K) or, with rowptr, the CSR range of a variable-width adjacency
         const int64_t base = rowptr ? rowptr[i] : i * K;
         int cnt = rowptr ? (int)(rowptr[i + 1] - base) : K;
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
         }
         if (slot == 0) {
 #pragma unroll
-            for (int q = 0; q < VEC; q++) dAB[i * 2 * hw + o0 + q] = dA[q];
+            for (int q = 0; q < VEC; q++) dAB[u * 2 * hw + o0 + q] = dA[q];
         }
     }
     // parameter gradients: slots -> lanes of slot 0 -> LDS across waves -> global
@@ -311,6 +312,18 @@ bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 
 extern "C" {
 
+int dgg_edgelist_topk_p_rows(const float *p_edge, int64_t N, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                             int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx, float *val,
+                             int32_t *eid, void *stream);
+int dgg_edge_mlp_bwd_rows(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *idx,
+                          const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
+                          const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
+                          int perturb, float *dAB, float *dpar, float *dex, void *stream);
+int dgg_edge_mlp_bwd_partp_rows(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int32_t *idx, const int32_t *eid,
+                                const float *val, const float *dval, const float *w, int K, const float *deg, const float *ex, const float *wdu,
+                                const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act, int perturb,
+                                const void *partp_ws, float *dz_rec, int64_t dz_rows, float *dAB, float *dpar, float *dex, void *stream);
+
 int dgg_edge_mlp_fwd(const float *AB, const float *xp, int64_t N, int h, int hw, const int32_t *erow, const int32_t *col,
                      int64_t E, const float *deg, const float *ex_in, int ex_mode, float t_ex, const float *wdu,
                      const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
@@ -328,12 +341,22 @@ int dgg_edge_mlp_fwd(const float *AB, const float *xp, int64_t N, int h, int hw,
 int dgg_edgelist_topk_p(const float *p_edge, int64_t N, const int64_t *rowptr, const int32_t *col, int noise_mode,
                         const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx, float *val, int32_t *eid,
                         void *stream) {
+    return dgg_edgelist_topk_p_rows(p_edge, N, 0, N, rowptr, col, noise_mode, G, ldG, s0, s1, K, idx, val, eid, stream);
+}
+
+// rows [row0, row1) of a row shard: rowptr [row1-row0+1] / col / p_edge are the shard's rebased CSR slice (rowptr[0] = 0), so eid
+// indexes the shard's own per-edge arrays; G and the outputs are the shard's rows; the noise is keyed on the global pair (row0 + i, j)
+int dgg_edgelist_topk_p_rows(const float *p_edge, int64_t N, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                             int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx, float *val,
+                             int32_t *eid, void *stream) {
     if (K < 1 || K > 64) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ELL width K must be in [1,64]");
     if (noise_mode == 1 && !G) return dgg_set_error(DGG_ERR_ARG, "explicit noise requested but G is NULL");
     if (noise_mode < 0 || noise_mode > 3)
         return dgg_set_error(DGG_ERR_UNSUPPORTED, "edgelist_topk_p: noise_mode must be none / explicit / hash / symmetric hash");
-    if (N == 0) return 0;
-    hipLaunchKernelGGL(edgelist_topk_p_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p_edge, N,
+    if (row0 < 0 || row1 < row0 || row1 > N) return dgg_set_error(DGG_ERR_ARG, "edgelist_topk_p: rows must satisfy 0 <= row0 <= row1 <= N");
+    const int64_t rows = row1 - row0;
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(edgelist_topk_p_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p_edge, rows, row0,
                        rowptr, col, noise_mode, G, ldG, s0, s1, K, idx, val, eid);
     return dgg_check_launch("edgelist_topk_p");
 }
@@ -345,6 +368,16 @@ int dgg_edge_mlp_bwd(const float *AB, int64_t N, int hw, const int64_t *rowptr, 
                      const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
                      const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
                      int perturb, float *dAB, float *dpar, float *dex, void *stream) {
+    return dgg_edge_mlp_bwd_rows(AB, N, hw, 0, N, rowptr, idx, eid, val, dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB,
+                                 dpar, dex, stream);
+}
+
+// rows [row0, row1) of a row shard: AB / dAB [N, 2*hw] and deg [N] are every node's, row i of the block (idx / eid / val / dval / dex,
+// rowptr when given) is node row0 + i -- its row side A_u, deg_u and dA_u are read / written at u = row0 + i
+int dgg_edge_mlp_bwd_rows(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *idx,
+                          const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
+                          const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
+                          int perturb, float *dAB, float *dpar, float *dex, void *stream) {
     if (!rowptr && (K < 1 || K > 64)) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ELL width K must be in [1,64]");
     const int vec = hw % 4 == 0 ? 4 : 1;
     const int lpe = hw / vec;
@@ -352,16 +385,18 @@ int dgg_edge_mlp_bwd(const float *AB, int64_t N, int hw, const int64_t *rowptr, 
         return dgg_set_error(DGG_ERR_UNSUPPORTED, "edge_mlp_bwd: hidden width must be 1, 2 or 4 x a power of two (<= 256)");
     if ((ex && (!wex || (!eid && !rowptr))) || (deg && (!wdu || !wdv)))
         return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd: missing extras / weights");
-    if (N == 0) return 0;
+    if (row0 < 0 || row1 < row0 || row1 > N) return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd: rows must satisfy 0 <= row0 <= row1 <= N");
+    const int64_t rows = row1 - row0;
+    if (rows == 0) return 0;
     static const int64_t gmax = getenv("DGG_EMLP_GRID") ? atoll(getenv("DGG_EMLP_GRID")) : 1024;   // (Pubmed shape: 103 us at 2048 workgroups, 85-89 at 512-1024, 123 at 128: row latency against contended parameter sums)
-    const unsigned grid = (unsigned)((N + 3) / 4 < gmax ? (N + 3) / 4 : gmax);
+    const unsigned grid = (unsigned)((rows + 3) / 4 < gmax ? (rows + 3) / 4 : gmax);
     const size_t lds = (size_t)4 * (5 * hw + 1) * sizeof(float);
     if (vec == 4)
-        hipLaunchKernelGGL(edge_mlp_bwd_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, N, hw, rowptr, idx, eid, val, dval, K,
-                           deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex);
+        hipLaunchKernelGGL(edge_mlp_bwd_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, rowptr, idx, eid, val,
+                           dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex);
     else
-        hipLaunchKernelGGL(edge_mlp_bwd_kernel<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, N, hw, rowptr, idx, eid, val, dval, K,
-                           deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex);
+        hipLaunchKernelGGL(edge_mlp_bwd_kernel<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, rowptr, idx, eid, val,
+                           dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex);
     return dgg_check_launch("edge_mlp_bwd");
 }
 
@@ -374,21 +409,33 @@ int dgg_edge_mlp_bwd_partp(const float *AB, int64_t N, int hw, const int32_t *id
                            const float *w, int K, const float *deg, const float *ex, const float *wdu, const float *wdv, const float *wex,
                            const float *b1, const float *w2, const float *b2, int act, int perturb, const void *partp_ws, int64_t ncols,
                            float *dz_rec, int64_t dz_rows, float *dAB, float *dpar, float *dex, void *stream) {
+    return dgg_edge_mlp_bwd_partp_rows(AB, ncols, hw, 0, N, idx, eid, val, dval, w, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb,
+                                       partp_ws, dz_rec, dz_rows, dAB, dpar, dex, stream);
+}
+
+// rows [row0, row1) of a row shard, as dgg_edge_mlp_bwd_rows: the payload partition is the shard's (dgg_partp_build of its [row1-row0, K]
+// block against ncols = N columns), AB / dAB / deg are every node's
+int dgg_edge_mlp_bwd_partp_rows(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int32_t *idx, const int32_t *eid,
+                                const float *val, const float *dval, const float *w, int K, const float *deg, const float *ex, const float *wdu,
+                                const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act, int perturb,
+                                const void *partp_ws, float *dz_rec, int64_t dz_rows, float *dAB, float *dpar, float *dex, void *stream) {
     if (K < 1 || K > 64) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ELL width K must be in [1,64]");
     const int lpe = hw / 4;
     if (hw % 4 != 0 || !pow2(lpe) || lpe > 64) return dgg_set_error(DGG_ERR_UNSUPPORTED, "edge_mlp_bwd_partp: hidden width must be 4 x a power of two (<= 256)");
     if ((ex && (!wex || !eid)) || (deg && (!wdu || !wdv)) || !w || !dz_rec || dz_rows <= 0)
         return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd_partp: missing extras / weights / scratch");
+    if (row0 < 0 || row1 < row0 || row1 > N) return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd_partp: rows must satisfy 0 <= row0 <= row1 <= N");
+    const int64_t rows = row1 - row0;
     const int *nodeptr = nullptr, *recpos = nullptr;
-    if (dgg_partp_internal_ptrs(partp_ws, N, K, ncols, &nodeptr, &recpos) != 0)
+    if (dgg_partp_internal_ptrs(partp_ws, rows, K, N, &nodeptr, &recpos) != 0)
         return dgg_set_error(DGG_ERR_UNSUPPORTED, "edge_mlp_bwd_partp: no payload partition with an entry -> record map for this block");
-    if (N == 0) return 0;
+    if (rows == 0) return 0;
     static const int64_t gmax = getenv("DGG_EMLP_GRID") ? atoll(getenv("DGG_EMLP_GRID")) : 1024;
-    const unsigned grid = (unsigned)((N + 3) / 4 < gmax ? (N + 3) / 4 : gmax);
+    const unsigned grid = (unsigned)((rows + 3) / 4 < gmax ? (rows + 3) / 4 : gmax);
     const size_t lds = (size_t)4 * (5 * hw + 1) * sizeof(float);
-    hipLaunchKernelGGL(edge_mlp_bwd_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, N, hw, (const int64_t *)nullptr, idx, eid, val, dval,
-                       K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex, w, recpos, dz_rec, dz_rows);
-    hipLaunchKernelGGL(edge_mlp_colsum, dim3((unsigned)((ncols * lpe + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nodeptr, ncols, dz_rec, dz_rows,
+    hipLaunchKernelGGL(edge_mlp_bwd_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, (const int64_t *)nullptr, idx, eid,
+                       val, dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex, w, recpos, dz_rec, dz_rows);
+    hipLaunchKernelGGL(edge_mlp_colsum, dim3((unsigned)((N * lpe + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nodeptr, N, dz_rec, dz_rows,
                        hw, dAB);
     return dgg_check_launch("edge_mlp_bwd_partp");
 }

@@ -148,12 +148,12 @@ __global__ __launch_bounds__(256) void edgelist_topk_kernel(
 // arithmetic) is applied while the sorted list is still in registers: w and the row sums come out of the same launch.
 template <int H>
 __device__ __forceinline__ void edgelist_row_full(
-    const int64_t i, const int lane, const float *__restrict__ xp, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, float t,
-    int noise_mode, const float *__restrict__ G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *__restrict__ idx,
+    const int64_t i, const int64_t row0, const int lane, const float *__restrict__ xp, const int64_t *__restrict__ rowptr,
+    const int32_t *__restrict__ col, float t, int noise_mode, const float *__restrict__ G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *__restrict__ idx,
     float *__restrict__ val, const float *__restrict__ kk, int mode, float *__restrict__ w, float *__restrict__ rs,
     int32_t *__restrict__ overflow) {
     const bool perturb = noise_mode != 0, sym = noise_mode == 3;
-    const float4 *xi4 = reinterpret_cast<const float4 *>(xp + i * H);
+    const float4 *xi4 = reinterpret_cast<const float4 *>(xp + (row0 + i) * H);      // (i: the block's row; row0 + i: its node)
     uint64_t list = DGG_EMPTY_KEY;
     const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
     for (int64_t eb = e0; eb < e1; eb += 64) {
@@ -185,7 +185,7 @@ __device__ __forceinline__ void edgelist_row_full(
             const float dist = c_sqrt(d2);
             float g = 0.0f;
             if (noise_mode == 1) g = G[i * ldG + j];
-            else if (noise_mode >= 2) g = pair_noise(s0, s1, (uint32_t)i, (uint32_t)j, sym);
+            else if (noise_mode >= 2) g = pair_noise(s0, s1, (uint32_t)(row0 + i), (uint32_t)j, sym);
             key = make_key(score_from_dist(dist, t, perturb, g), j);
         }
         key = wave_sort_desc(key, lane);
@@ -225,7 +225,7 @@ __device__ __forceinline__ void edgelist_row_full(
 // the other, made the slowest wavefront -- four rows, one of them a hub of 300 -- the whole launch: 45 us).
 template <int H>
 __global__ __launch_bounds__(256) void edgelist_topk_pack4(
-    const float *__restrict__ xp, int64_t N, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, float t,
+    const float *__restrict__ xp, int64_t N, int64_t row0, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, float t,
     int noise_mode, const float *__restrict__ G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *__restrict__ idx,
     float *__restrict__ val, const float *__restrict__ kk, int mode, float *__restrict__ w, float *__restrict__ rs,
     int32_t *__restrict__ overflow, unsigned npack) {
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void edgelist_topk_pack4(
     if (blockIdx.x >= npack) {                                    // one wavefront per row: the rows wider than a lane group
         const int64_t iw = (int64_t)(blockIdx.x - npack) * (blockDim.x >> 6) + dgg::wave_id();
         if (iw >= N || rowptr[iw + 1] - rowptr[iw] <= 16) return;
-        edgelist_row_full<H>(iw, lane, xp, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, kk, mode, w, rs, overflow);
+        edgelist_row_full<H>(iw, row0, lane, xp, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, kk, mode, w, rs, overflow);
         return;
     }
     const int64_t i0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + dgg::wave_id()) * 4;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void edgelist_topk_pack4(
     const bool perturb = noise_mode != 0, sym = noise_mode == 3;
     const bool have = rowok && l < n;
     const int32_t j = have ? col[e0 + l] : 0;
-    const float4 *xi4 = reinterpret_cast<const float4 *>(xp + (rowok ? i : 0) * H);
+    const float4 *xi4 = reinterpret_cast<const float4 *>(xp + (rowok ? row0 + i : 0) * H);
     const float4 *xj4 = reinterpret_cast<const float4 *>(xp + (int64_t)j * H);
     float d2 = 0.0f;
     constexpr int CH = H / 4 < 8 ? H / 4 : 8;                     // float4s of each operand in flight per lane
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void edgelist_topk_pack4(
         const float dist = c_sqrt(d2);
         float gn = 0.0f;
         if (noise_mode == 1) gn = G[i * ldG + j];
-        else if (noise_mode >= 2) gn = pair_noise(s0, s1, (uint32_t)i, (uint32_t)j, sym);
+        else if (noise_mode >= 2) gn = pair_noise(s0, s1, (uint32_t)(row0 + i), (uint32_t)j, sym);
         key = make_key(score_from_dist(dist, t, perturb, gn), j);
     }
     // descending sort inside every group of 16 lanes: blocks of 2, 4, 8 as in wave_sort, the last merge with the final direction
@@ -319,14 +319,14 @@ __global__ __launch_bounds__(256) void edgelist_topk_pack4(
 
 template <int H>
 __global__ __launch_bounds__(256) void edgelist_topk_vec(
-    const float *__restrict__ xp, int64_t N, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, float t,
+    const float *__restrict__ xp, int64_t N, int64_t row0, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, float t,
     int noise_mode, const float *__restrict__ G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *__restrict__ idx,
     float *__restrict__ val, const float *__restrict__ kk, int mode, float *__restrict__ w, float *__restrict__ rs,
     int32_t *__restrict__ overflow) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + dgg::wave_id();
     if (i >= N) return;
-    edgelist_row_full<H>(i, lane, xp, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, kk, mode, w, rs, overflow);
+    edgelist_row_full<H>(i, row0, lane, xp, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, kk, mode, w, rs, overflow);
 }
 
 // same for latent widths beyond 128 (PPI: 2048): the candidates of a row are scored ONE AT A TIME by the whole wavefront --
@@ -466,7 +466,7 @@ namespace {
 inline bool edgelist_vec_ok(const float *xp, int h) {
     return (h == 16 || h == 32 || h == 64 || h == 128) && (uintptr_t)xp % 16 == 0;
 }
-void launch_edgelist_vec(const float *xp, int64_t N, int h, const int64_t *rowptr, const int32_t *col, float t, int noise_mode,
+void launch_edgelist_vec(const float *xp, int64_t N, int64_t row0, int h, const int64_t *rowptr, const int32_t *col, float t, int noise_mode,
                          const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx, float *val, const float *k,
                          int mode, float *w, float *rs, int32_t *overflow, hipStream_t st) {
     // (four rows per wavefront -- see edgelist_topk_pack4; DGG_EL_PACK=0 keeps a wavefront per row)
@@ -474,9 +474,9 @@ void launch_edgelist_vec(const float *xp, int64_t N, int h, const int64_t *rowpt
     const unsigned npack = (unsigned)((N + 15) / 16);
     const dim3 grid((unsigned)(pack ? npack + (N + 3) / 4 : (N + 3) / 4)), block(256);
 #define DGG_EL_VEC(HH)                                                                                                       \
-    if (pack) hipLaunchKernelGGL(edgelist_topk_pack4<HH>, grid, block, 0, st, xp, N, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, \
+    if (pack) hipLaunchKernelGGL(edgelist_topk_pack4<HH>, grid, block, 0, st, xp, N, row0, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, \
                                  k, mode, w, rs, overflow, npack);                                                           \
-    else hipLaunchKernelGGL(edgelist_topk_vec<HH>, grid, block, 0, st, xp, N, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, k, \
+    else hipLaunchKernelGGL(edgelist_topk_vec<HH>, grid, block, 0, st, xp, N, row0, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, k, \
                             mode, w, rs, overflow)
     if (h == 16) { DGG_EL_VEC(16); }
     else if (h == 32) { DGG_EL_VEC(32); }
@@ -487,6 +487,10 @@ void launch_edgelist_vec(const float *xp, int64_t N, int h, const int64_t *rowpt
 }  // namespace
 
 extern "C" {
+
+int dgg_edgelist_topk_softk_rows(const float *xp, int64_t N, int h, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                                 float t, int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, const float *k,
+                                 int mode, int32_t *idx, float *val, float *w, float *rs, int32_t *overflow, void *stream);
 
 int dgg_edgelist_topk(const float *xp, int64_t N, int h, const int64_t *rowptr, const int32_t *col, float t,
                       int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx,
@@ -500,7 +504,7 @@ int dgg_edgelist_topk(const float *xp, int64_t N, int h, const int64_t *rowptr, 
         hipLaunchKernelGGL(edgelist_topk_wide_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, xp, N, h,
                            rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val);
     else if (edgelist_vec_ok(xp, h))
-        launch_edgelist_vec(xp, N, h, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, nullptr, 0, nullptr, nullptr, nullptr,
+        launch_edgelist_vec(xp, N, 0, h, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, nullptr, 0, nullptr, nullptr, nullptr,
                             (hipStream_t)stream);
     else
         hipLaunchKernelGGL(edgelist_topk_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, xp, N, h,
@@ -513,16 +517,27 @@ int dgg_edgelist_topk(const float *xp, int64_t N, int h, const int64_t *rowptr, 
 int dgg_edgelist_topk_softk(const float *xp, int64_t N, int h, const int64_t *rowptr, const int32_t *col, float t,
                             int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, const float *k,
                             int mode, int32_t *idx, float *val, float *w, float *rs, int32_t *overflow, void *stream) {
+    return dgg_edgelist_topk_softk_rows(xp, N, h, 0, N, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, k, mode, idx, val, w, rs, overflow,
+                                        stream);
+}
+
+// the rows [row0, row1) of a row shard: rowptr [row1-row0+1] / col are the shard's rebased CSR slice (rowptr[0] = 0, global columns),
+// xp [N,h] every node; k, G and the outputs are the shard's rows.  The noise is keyed on the global pair (row0 + i, j).
+int dgg_edgelist_topk_softk_rows(const float *xp, int64_t N, int h, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                                 float t, int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, const float *k,
+                                 int mode, int32_t *idx, float *val, float *w, float *rs, int32_t *overflow, void *stream) {
     if (K < 1 || K > 64) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ELL width K must be in [1,64]");
     if (noise_mode == 1 && !G) return dgg_set_error(DGG_ERR_ARG, "explicit noise requested but G is NULL");
     if (noise_mode < 0 || noise_mode > 3)
         return dgg_set_error(DGG_ERR_UNSUPPORTED, "edgelist_topk: noise_mode must be none / explicit / hash / symmetric hash");
     if (mode != 0 && mode != 1 && mode != 3) return dgg_set_error(DGG_ERR_ARG, "edgelist_topk_softk: mode must be 0 (k_times), 1 (k_only) or 3 (hard)");
     if (!k || !w || !rs) return dgg_set_error(DGG_ERR_ARG, "edgelist_topk_softk: k, w and rs are required");
+    if (row0 < 0 || row1 < row0 || row1 > N) return dgg_set_error(DGG_ERR_ARG, "edgelist_topk_softk: rows must satisfy 0 <= row0 <= row1 <= N");
     if (!edgelist_vec_ok(xp, h))
         return dgg_set_error(DGG_ERR_UNSUPPORTED, "edgelist_topk_softk: latent_dim must be 16, 32, 64 or 128 (16-byte aligned rows)");
-    if (N == 0) return 0;
-    launch_edgelist_vec(xp, N, h, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, k, mode, w, rs, overflow, (hipStream_t)stream);
+    if (row1 == row0) return 0;
+    launch_edgelist_vec(xp, row1 - row0, row0, h, rowptr, col, t, noise_mode, G, ldG, s0, s1, K, idx, val, k, mode, w, rs, overflow,
+                        (hipStream_t)stream);
     return dgg_check_launch("edgelist_topk_softk");
 }
 

@@ -411,6 +411,9 @@ class _FusedDGGMlpConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, deg, layer, sc_static, Wcat, wdu, wdv, wex, b1, w2, b2, *params):
         x, params, ctx.d_orig = _pad_features(x, params, layer.PARAM_KEYS)
+        if layer.x_full is not None:                     # replicated features on a row shard (as in _FusedDGGConvFn.forward)
+            layer.x_full, x = x, x[layer.r0:layer.r1]
+        ctx.x_full = layer.x_full
         P = dict(zip(layer.PARAM_KEYS, params))
         det = lambda t_: None if t_ is None else t_.detach()  # noqa: E731
         ctx.packed = packed = sc_static.get("packed")
@@ -435,6 +438,7 @@ class _FusedDGGMlpConvFn(torch.autograd.Function):
         layer = ctx.layer
         P = dict(zip(layer.PARAM_KEYS, params))
         layer.saved, layer._fwd_gen, layer.scorer = ctx.state, ctx.state["gen"], ctx.scorer
+        layer.x_full = ctx.x_full
         layer.x_grad = bool(ctx.needs_input_grad[0])
         if dZ is None:
             dZ = torch.zeros_like(ctx.state["Z"])
@@ -780,7 +784,7 @@ class DGG_LearnableK_debug(nn.Module):
         if st.get("partp") is None:                           # (shape outside the partitioned backward: the separate modules)
             return self._fused_fallback("shape outside the partitioned backward")
         k = st["k"]
-        if cand is not None and self._wide_rows(in_adj, rowptr, k):
+        if cand is not None and self._wide_rows(in_adj, rowptr, k, layer):
             # rows wider than the ELL with learned degrees beyond it: the CSR form from here on (this forward is discarded, once per graph)
             if not mlp_mode and "_overflow_scratch" in self.__dict__:
                 self._overflow_scratch.zero_()
@@ -795,7 +799,7 @@ class DGG_LearnableK_debug(nn.Module):
         elif mlp_mode:
             ent = self.__dict__.get("_wide_cache", {}).get(id(in_adj))
             if not (ent is not None and ent[0]() is in_adj and ent[1] <= self.ell_width):     # (no row can outgrow the list otherwise)
-                self._track_overflow(k, rowptr[1:] - rowptr[:-1])
+                self._track_overflow(k, self._row_lens(rowptr, layer))
         elif __import__("os").environ.get("DGG_STRICT_BOUND") == "1":
             self.check_ell_bound()
         unnorm = EllAdjacency(st["idx"], st["w"], N, rs=st["rs"], k=k, score=st["val"], owner=self, layout=lay)
@@ -912,21 +916,36 @@ class DGG_LearnableK_debug(nn.Module):
             return False
         return True if ent[2] else None
 
-    def _wide_rows(self, in_adj, rowptr, k):
+    def _wide_rows(self, in_adj, rowptr, k, layer=None):
         """Should this forward go through the CSR form of select_top_k instead of the 64-wide ELL?  While a graph with rows wider than
         the ELL is UNDECIDED the learned degrees are tested on the device and one flag is read back on EVERY forward (one host
         synchronisation; round 4 read it every 16th forward only, and the forwards in between could truncate a row -- ADVICE round 4);
         the first forward that needs the CSR form makes the decision sticky.  While a hipGraph is being captured nothing can be read
-        back: the list is used and its bound enforced (check_ell_bound)."""
+        back: the list is used and its bound enforced (check_ell_bound).
+        layer: the engine of this forward.  On a row shard k holds the shard's rows, and on several ranks the decision is COLLECTIVE:
+        every rank ORs its flag into one MAX all-reduce in the same forward (the graph's widest row -- the same on every rank -- decides
+        whether a graph is undecided), so all ranks take the same branch and none waits in a collective the others skip."""
         st = self._wide_rows_state(in_adj, rowptr)
         if st is not None:
             return st
         if _capturing():
             return False
         ent = self._wide_cache[id(in_adj)]
-        lens = rowptr[1:] - rowptr[:-1]
-        ent[2] = bool(((k.detach() + 8.5 > float(self.ell_width)) & (lens > self.ell_width)).any().item())
+        flag = ((k.detach() + 8.5 > float(self.ell_width)) & (self._row_lens(rowptr, layer) > self.ell_width)).any()
+        if layer is not None and layer.coll:
+            import torch.distributed as dist
+            flag = flag.to(torch.int32).reshape(1)
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=layer.group)
+        ent[2] = bool(flag.item())
         return ent[2]
+
+    @staticmethod
+    def _row_lens(rowptr, layer=None):
+        """candidates per row of the forward's rows: the whole graph's, or a row shard's rows [r0, r1) of it"""
+        lens = rowptr[1:] - rowptr[:-1]
+        if layer is not None and (layer.r0, layer.r1) != (0, layer.N):
+            lens = lens[layer.r0:layer.r1]
+        return lens
 
     # ---- all-pairs candidates whose learned degrees outgrow the 64-wide list --------------------------------------------------
     def _allpairs_pattern(self, N, device):

@@ -2,6 +2,7 @@
 
     net = ShardedGCN_DGG(model)                     # shares model's parameters, state_dict and optimiser groups
     logp, adj, _ = net(x, AllPairs(deg))            # x [N, d] and deg [N] replicated; logp = this rank's rows net.rows
+    logp, adj, _ = net(x, in_adj)                   # or edge-list candidates: in_adj the whole sparse [N, N] graph, replicated
     loss = global_nll_loss(logp, labels, idx_train, net.rows)
     loss.backward()                                 # every rank now holds the full-graph gradient of every parameter
 
@@ -9,6 +10,13 @@ Layer 1 (generator + normalize_adj + GCNConv) is the fused node of DGG_Learnable
 dgg_amd.parallel.ShardedDGGConv on replicated features with the hybrid exchange; layer 2 is relu(Â_local (x1 W2)) over all N columns
 with x1 W2 (or x1) all-gathered and its cotangent reduce-scattered (_ShardedConvFn).  Both layers sum the replicated weight gradients
 over the ranks inside their autograd nodes, so identical optimisers keep the ranks' parameters bit-identical.
+
+Edge-list candidates (a sparse in_adj, the reference's own configuration: dgm.py:1613-1614) run on several ranks with the u-v-dist scorer
+and the edge-MLP scorers of the fused layer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv, A_uv), under no / hash / symmetric hash noise:
+every rank scores its own rows' candidates through the row-range kernels, and the scorer's gradients are summed with the layer's.  Rows
+wider than the 64-rank list whose learned degree needs more ranks than that (the one-GPU model's CSR form) are not sharded: that forward
+raises NotImplementedError on every rank at once (the flag is ORed over the ranks).  How the step scales with the number of GPUs has not
+been measured.
 
 The reference has no distributed code; its loss is F.nll_loss(out[idx], labels[idx])
 (train_small_graphs.py:226), which global_nll_loss splits over the ranks.
@@ -21,7 +29,7 @@ import torch.nn.functional as F
 from . import ops
 from .adjacency import AllPairs
 from .dgm import _capturing
-from .model import GCN_DGG
+from .model import GCN_DGG, _with_self_loops
 from .parallel import ShardedDGGConv, _all_gather_rows, shard_bounds
 
 
@@ -101,14 +109,15 @@ class ShardedGCN_DGG(nn.Module):
     The wrapper owns no parameters of its own: it holds `model` (whose parameters it broadcasts from the group's first rank when
     there are several), and `state_dict()` / `load_state_dict()` / `params1` / `params2` are the model's, so checkpoints and the
     optimiser groups of train_small_graphs.py are unchanged.  forward(x, in_adj) takes the FULL features x [N, d] (data, replicated on
-    every rank) and in_adj = AllPairs(prior degrees of all N nodes); it returns (log_probs of the rank's rows, the DETACHED unnormalised
+    every rank) and in_adj = AllPairs(prior degrees of all N nodes) or the whole graph's sparse [N, N] adjacency (edge-list candidates,
+    replicated like x; self loops are added as GCN_DGG.forward adds them); it returns (log_probs of the rank's rows, the DETACHED unnormalised
     EllAdjacency of those rows with global column indices, None).  After backward() every rank holds the full-graph gradient of every
     parameter when the loss is global_nll_loss (or any loss whose per-rank parts sum to the whole).
 
     Every rank must draw the same noise: seed the CPU generator identically on every rank (torch.manual_seed) or call
     model.dggs[0].set_seed.  The dropout between the layers draws each rank's mask from its own CUDA generator.
-    Outside its coverage the wrapper raises (no silent fall-back): edge-list candidates on several ranks (one rank: the model itself
-    runs them), a writer, configurations the fused layer declines, a hipGraph capture on several ranks, args.dgg_hard_literal,
+    Outside its coverage the wrapper raises (no silent fall-back), before any collective: on several ranks, edge-list candidates whose
+    rows need the CSR form (raised by every rank in the same forward), a writer, configurations the fused layer declines, a hipGraph capture on several ranks, args.dgg_hard_literal,
     args.dgg_differentiable_adj, args.dgg_wide_rows other than 'auto' / 'chunked', and on several ranks args.dgg_sym_generator = 'auto'
     (a generator switch decided from one rank's rows)."""
 
@@ -150,22 +159,37 @@ class ShardedGCN_DGG(nn.Module):
         return self._rows
 
     # ------------------------------------------------------------------------------------------------------------------------------
+    def _edge_lists(self, in_adj):
+        """edge-list candidates on several ranks: the row shard's own path (one rank: the model's step)"""
+        return self.world > 1 and not isinstance(in_adj, AllPairs)
+
     def _check(self, x, in_adj, writer):
         m = self.module
         dgg, a = m.dggs[0], m.dggs[0].args
+        # (every refusal of edge-list candidates on several ranks names them)
+        what = "ShardedGCN_DGG (edge-list candidates on several ranks)" if self._edge_lists(in_adj) else "ShardedGCN_DGG"
         if writer is not None:
-            raise NotImplementedError("ShardedGCN_DGG: a writer (histograms of the whole graph) is not supported on a row shard")
-        if self.world > 1 and not isinstance(in_adj, AllPairs):
-            raise NotImplementedError("ShardedGCN_DGG: edge-list candidates run on one rank (in_adj must be AllPairs(prior_degree) when "
-                                      "the group has several ranks)")
+            raise NotImplementedError(f"{what}: a writer (histograms of the whole graph) is not supported on a row shard")
         if self.world > 1 and _capturing():
-            raise NotImplementedError("ShardedGCN_DGG: a hipGraph capture of a step on several ranks is not supported")
+            raise NotImplementedError(f"{what}: a hipGraph capture of a step on several ranks is not supported")
         if getattr(a, "dgg_hard_literal", False):
-            raise NotImplementedError("ShardedGCN_DGG: args.dgg_hard_literal is not supported")
+            raise NotImplementedError(f"{what}: args.dgg_hard_literal is not supported")
         if m.differentiable_adj:
-            raise NotImplementedError("ShardedGCN_DGG: args.dgg_differentiable_adj needs the separate modules (one GPU: the model itself)")
+            raise NotImplementedError(f"{what}: args.dgg_differentiable_adj needs the separate modules (one GPU: the model itself)")
         if x.requires_grad:
-            raise ValueError("ShardedGCN_DGG: the features are data replicated on every rank; they cannot take a gradient")
+            raise ValueError(f"{what}: the features are data replicated on every rank; they cannot take a gradient")
+        if self._edge_lists(in_adj):
+            if not isinstance(in_adj, torch.Tensor) or in_adj.dim() != 2 or in_adj.shape[0] != x.shape[0] or in_adj.shape[1] != x.shape[0]:
+                raise NotImplementedError(f"{what}: in_adj must be AllPairs(prior_degree) or the whole graph's [N, N] adjacency "
+                                          f"(N = {x.shape[0]}, got {type(in_adj).__name__} {tuple(getattr(in_adj, 'shape', ()))})")
+            policy = getattr(a, "dgg_wide_rows", "auto")
+            if policy not in ("auto", "chunked"):
+                raise NotImplementedError(f"{what}: args.dgg_wide_rows = {policy!r} (a row shard keeps the 64-rank list; the CSR form of "
+                                          "rows wider than it is not sharded)")
+            why = dgg._fused_outside(x, in_adj, m.conv1.W)
+            if why is not None:
+                raise NotImplementedError(f"{what}: the fused layer does not cover this configuration ({why})")
+            return
         if not isinstance(in_adj, AllPairs):
             return
         if in_adj.prior_degree.shape[0] != x.shape[0]:
@@ -186,12 +210,20 @@ class ShardedGCN_DGG(nn.Module):
         self._check(x, in_adj, writer)
         N = x.shape[0]
         self._rows = shard_bounds(N, self.world, self.rank)[:2]
-        if not isinstance(in_adj, AllPairs):                 # (one rank: edge-list candidates are the model's own step)
+        edge_lists = self._edge_lists(in_adj)
+        if not isinstance(in_adj, AllPairs) and not edge_lists:     # (one rank: edge-list candidates are the model's own step)
             return m(x, in_adj, noise=noise, epoch=epoch, writer=writer)
+        if edge_lists:
+            in_adj = _with_self_loops(in_adj)                # (as GCN_DGG.forward: cached per graph object)
         eng = self._engine
         if eng is None or eng.N != N:
             eng = self._engine = ShardedDGGConv(ops, N, group=self.group, K=64, t=ops.T_DIST, x_full=x, hybrid=True)
         got = m.dggs[0]._forward_conv(x, in_adj, m.conv1.W, True, engine=eng)
+        if got is None and edge_lists:
+            # (decided collectively: _wide_rows ORs the ranks' flags, so every rank raises here in the same forward)
+            raise NotImplementedError("ShardedGCN_DGG (edge-list candidates on several ranks): a row wider than the 64-rank list has a "
+                                      "learned degree beyond it; the CSR form of such rows is not sharded "
+                                      f"({m.dggs[0].__dict__.get('fused_fallback', {})})")
         if got is None:
             raise NotImplementedError("ShardedGCN_DGG: this forward left the fused layer's coverage "
                                       f"({m.dggs[0].__dict__.get('fused_fallback', {})})")

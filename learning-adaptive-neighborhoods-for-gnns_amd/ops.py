@@ -563,25 +563,36 @@ def edgelist_topk(xp, rowptr, col, K=DEFAULT_K, t=T_DIST, noise_mode=NOISE_NONE,
 
 
 def edgelist_topk_softk(xp, rowptr, col, k, mode=MODE_K_TIMES_EDGE_PROB, K=DEFAULT_K, t=T_DIST, noise_mode=NOISE_NONE, G=None, seed=(0, 0),
-                        overflow=None):
+                        overflow=None, rows=None):
     """edgelist_topk + softk_fwd in one launch (same bits): -> idx, val, w, rs; None when the latent width is not 16 / 32 / 64 / 128.
-    overflow (int32[1] device tensor, optional): ORed with 1 when a row with more than K candidates has k + 8.5 > K."""
+    overflow (int32[1] device tensor, optional): ORed with 1 when a row with more than K candidates has k + 8.5 > K.
+    rows = (r0, r1): the rows of a row shard (dgg_edgelist_topk_softk_rows) -- xp holds every node, (rowptr, col) is the shard's rebased
+    CSR slice (rowptr [r1-r0+1] from 0, global columns: parallel.csr_rows), k and the outputs are the shard's rows; the noise is the whole
+    graph's (keyed on global ids).  rows=None: the whole graph, exactly the call without it."""
     xp = _chk(xp)
     N, h = xp.shape
     if h not in (16, 32, 64, 128):
         return None
     rowptr, col, k = _chk(rowptr, torch.int64), _chk(col, torch.int32), _chk(k)
-    idx = torch.empty((N, K), device=xp.device, dtype=torch.int32)
-    val = torch.empty((N, K), device=xp.device, dtype=torch.float32)
-    w = torch.empty((N, K), device=xp.device, dtype=torch.float32)
-    rs = torch.empty((N,), device=xp.device, dtype=torch.float32)
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    n = r1 - r0
+    assert rowptr.shape[0] == n + 1 and k.shape[0] == n, "edgelist_topk_softk: rowptr [rows+1] and k [rows] of the rows asked for"
+    idx = torch.empty((n, K), device=xp.device, dtype=torch.int32)
+    val = torch.empty((n, K), device=xp.device, dtype=torch.float32)
+    w = torch.empty((n, K), device=xp.device, dtype=torch.float32)
+    rs = torch.empty((n,), device=xp.device, dtype=torch.float32)
     ldG = 0
     if G is not None:
         G = _chk(G)
         ldG = N
     pe = _probe_begin()
-    _lib.check(_lib.lib().dgg_edgelist_topk_softk(_ptr(xp), N, h, _ptr(rowptr), _ptr(col), t, noise_mode, _ptr(G), ldG, seed[0], seed[1],
-                                                  K, _ptr(k), mode, _ptr(idx), _ptr(val), _ptr(w), _ptr(rs), _ptr(overflow), _stream()), "edgelist_topk_softk")
+    if rows is None:
+        _lib.check(_lib.lib().dgg_edgelist_topk_softk(_ptr(xp), N, h, _ptr(rowptr), _ptr(col), t, noise_mode, _ptr(G), ldG, seed[0], seed[1],
+                                                      K, _ptr(k), mode, _ptr(idx), _ptr(val), _ptr(w), _ptr(rs), _ptr(overflow), _stream()), "edgelist_topk_softk")
+    elif n > 0:
+        _lib.check(_lib.lib().dgg_edgelist_topk_softk_rows(_ptr(xp), N, h, r0, r1, _ptr(rowptr), _ptr(col), t, noise_mode, _ptr(G), ldG, seed[0],
+                                                           seed[1], K, _ptr(k), mode, _ptr(idx), _ptr(val), _ptr(w), _ptr(rs), _ptr(overflow),
+                                                           _stream()), "edgelist_topk_softk_rows")
     _probe_end("edgelist_topk", pe)
     return idx, val, w, rs
 
@@ -647,28 +658,42 @@ def edge_mlp_fwd(AB, xp, erow, col, deg, ex_in, ex_mode, t_ex, wdu, wdv, wex, b1
     return p_edge, ex_out
 
 
-def edgelist_topk_p(p_edge, N, rowptr, col, K=DEFAULT_K, noise_mode=NOISE_NONE, G=None, seed=(0, 0)):
-    """perturbation + per-row top-K on given edge probabilities -> idx, val, eid [N,K]"""
+def edgelist_topk_p(p_edge, N, rowptr, col, K=DEFAULT_K, noise_mode=NOISE_NONE, G=None, seed=(0, 0), rows=None):
+    """perturbation + per-row top-K on given edge probabilities -> idx, val, eid [N,K].
+    rows = (r0, r1): the rows of a row shard (dgg_edgelist_topk_p_rows) -- (rowptr, col) and p_edge are the shard's rebased CSR slice
+    (parallel.csr_rows), N the whole graph's node count; the outputs are [r1-r0, K] and eid indexes the shard's per-edge arrays."""
     p_edge = _chk(p_edge)
     rowptr, col = _chk(rowptr, torch.int64), _chk(col, torch.int32)
-    idx = torch.empty((N, K), device=p_edge.device, dtype=torch.int32)
-    val = torch.empty((N, K), device=p_edge.device, dtype=torch.float32)
-    eid = torch.empty((N, K), device=p_edge.device, dtype=torch.int32)
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    n = r1 - r0
+    assert rowptr.shape[0] == n + 1, "edgelist_topk_p: rowptr [rows+1] of the rows asked for"
+    idx = torch.empty((n, K), device=p_edge.device, dtype=torch.int32)
+    val = torch.empty((n, K), device=p_edge.device, dtype=torch.float32)
+    eid = torch.empty((n, K), device=p_edge.device, dtype=torch.int32)
     ldG = 0
     if G is not None:
         G = _chk(G)
         ldG = G.shape[-1]
-    _lib.check(_lib.lib().dgg_edgelist_topk_p(_ptr(p_edge), N, _ptr(rowptr), _ptr(col), noise_mode, _ptr(G), ldG, seed[0], seed[1], K,
-                                              _ptr(idx), _ptr(val), _ptr(eid), _stream()), "edgelist_topk_p")
+    if rows is None:
+        _lib.check(_lib.lib().dgg_edgelist_topk_p(_ptr(p_edge), N, _ptr(rowptr), _ptr(col), noise_mode, _ptr(G), ldG, seed[0], seed[1], K,
+                                                  _ptr(idx), _ptr(val), _ptr(eid), _stream()), "edgelist_topk_p")
+    elif n > 0:
+        _lib.check(_lib.lib().dgg_edgelist_topk_p_rows(_ptr(p_edge), N, r0, r1, _ptr(rowptr), _ptr(col), noise_mode, _ptr(G), ldG, seed[0],
+                                                       seed[1], K, _ptr(idx), _ptr(val), _ptr(eid), _stream()), "edgelist_topk_p_rows")
     return idx, val, eid
 
 
 def edge_mlp_bwd(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, act=ACT_LEAKY, perturb=False, need_dex=False,
-                 rowptr=None, partp=None, w=None, nrec_max=0):
+                 rowptr=None, partp=None, w=None, nrec_max=0, rows=None):
     """-> dAB [N,2hw], dpar [5hw+1] = [dwdu|dwdv|dwex|db1|dw2|db2], dex (shape of dval) or None.
     ELL adjacency: idx/eid/val/dval [N,K]; CSR-valued adjacency: rowptr given, idx = col [E], val/dval [E], eid None.
     partp (+ w, the weights it was built from, and nrec_max >= its number of records, e.g. the number of candidate edges): the
-    neighbour-side sums without float atomics (dgg_edge_mlp_bwd_partp)"""
+    neighbour-side sums without float atomics (dgg_edge_mlp_bwd_partp).
+    rows = (r0, r1): the block holds rows [r0, r1) of a row shard (dgg_edge_mlp_bwd_rows / _partp_rows): AB, deg and dAB are every node's,
+    idx / eid / val / dval / w / dex (and rowptr) the shard's rows, partp the shard's partition against all N columns."""
+    if rows is not None:
+        return _edge_mlp_bwd_rows(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, need_dex, rowptr, partp, w,
+                                  nrec_max, rows)
     AB = _chk(AB)
     N = AB.shape[0]
     K = idx.shape[1] if rowptr is None else 0
@@ -689,6 +714,34 @@ def edge_mlp_bwd(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, ac
                                            _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)),
                                            _ptr(_chk(b2)), act, int(perturb), _ptr(dAB), _ptr(dpar), _ptr(dex), _stream()),
                "edge_mlp_bwd")
+    return dAB, dpar, dex
+
+
+def _edge_mlp_bwd_rows(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, need_dex, rowptr, partp, w, nrec_max, rows):
+    AB = _chk(AB)
+    N = AB.shape[0]
+    r0, r1 = int(rows[0]), int(rows[1])
+    n = r1 - r0
+    K = idx.shape[1] if rowptr is None else 0
+    assert rowptr is not None or idx.shape[0] == n, "edge_mlp_bwd: idx [rows, K] of the rows asked for"
+    hw = AB.shape[1] // 2
+    zz = _zeros((N * 2 * hw + 5 * hw + 1,), AB.device)
+    dAB, dpar = zz[:N * 2 * hw].view(N, 2 * hw), zz[N * 2 * hw:]
+    dex = torch.empty(tuple(dval.shape), device=AB.device, dtype=torch.float32) if need_dex else None
+    if n == 0:
+        return dAB, dpar, dex
+    o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
+    if (EMLP_BWD_PARTP and partp is not None and w is not None and nrec_max > 0 and rowptr is None and hw % 4 == 0 and partp.layout is None
+            and partp.rows == n and partp.ncols == N and partp_has_map(n)):
+        dz = torch.empty((int(nrec_max) * hw,), device=AB.device, dtype=torch.float32)
+        _lib.check(_lib.lib().dgg_edge_mlp_bwd_partp_rows(_ptr(AB), N, hw, r0, r1, _ptr(idx), _ptr(eid), _ptr(_chk(val)), _ptr(_chk(dval)), _ptr(_chk(w)),
+                                                          K, _ptr(o(deg)), _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)),
+                                                          _ptr(_chk(w2)), _ptr(_chk(b2)), act, int(perturb), _ptr(partp.ws), _ptr(dz), int(nrec_max),
+                                                          _ptr(dAB), _ptr(dpar), _ptr(dex), _stream()), "edge_mlp_bwd_partp_rows")
+        return dAB, dpar, dex
+    _lib.check(_lib.lib().dgg_edge_mlp_bwd_rows(_ptr(AB), N, hw, r0, r1, _ptr(rowptr), _ptr(idx), _ptr(eid), _ptr(_chk(val)), _ptr(_chk(dval)), K,
+                                                _ptr(o(deg)), _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)),
+                                                _ptr(_chk(b2)), act, int(perturb), _ptr(dAB), _ptr(dpar), _ptr(dex), _stream()), "edge_mlp_bwd_rows")
     return dAB, dpar, dex
 
 

@@ -50,6 +50,14 @@ def shard_bounds(N, world, rank):
     return r0, min(r0 + per, N), per
 
 
+def csr_rows(rowptr, col, rows):
+    """-> (rowptr [r1-r0+1] from 0, col of rows [r0, r1), (e0, e1)): the rebased CSR slice the row-shard entries of the edge-list kernels
+    take (include/dgg_hip.h, dgg_edgelist_topk_softk_rows); per-edge arrays are sliced to [e0, e1).  One host read of two offsets."""
+    r0, r1 = int(rows[0]), int(rows[1])
+    e0, e1 = (int(v) for v in rowptr[[r0, r1]].tolist())
+    return (rowptr[r0:r1 + 1] - e0).contiguous(), col[e0:e1], (e0, e1)
+
+
 class _Gather:
     """A (possibly still running) all-gather of row shards: .get() waits and returns the [N, ...] tensor.  On RCCL the
     wait is a stream dependency (no host block); shards are padded to `per` rows for the fixed-size collective.  `bufs`
@@ -94,8 +102,10 @@ def _all_gather_rows(t_local, N, per, group, bufs=None, key=None):
 
 
 class ShardedDGGConv:
-    """One DGG (all-pairs, u-v-dist / x / k_times_edge_prob) + normalise + GCNConv layer, forward and backward,
-    on a row shard.  Parameters are a dict with the reference's names (dgm.py:1097-1143, model.py:583)."""
+    """One DGG (all-pairs or edge-list candidates; u-v-dist or, on edge lists, an edge-MLP scorer / x / k_times_edge_prob) + normalise +
+    GCNConv layer, forward and backward, on a row shard.  Parameters are a dict with the reference's names (dgm.py:1097-1143, model.py:583).
+    Edge-list candidates on several ranks need replicated features (x_full): every rank projects xp (and the edge-MLP scorer's AB) for all
+    N nodes, scores its own rows' candidates and sums the scorer's gradients with the layer's in one all-reduce."""
 
     PARAM_KEYS = ("We", "be", "Wk", "bk", "W1", "b1", "Wmu", "bmu", "Wp", "bp", "Wc")
 
@@ -104,7 +114,10 @@ class ShardedDGGConv:
         self.kern, self.N, self.group = kern, N, group
         # cand = (rowptr int64 [N+1], col int32 [E]): the candidates of row i are the stored entries of in_adj (edge-list mode, the
         # live class's semantics dgm.py:1613-1614) instead of all N columns; every candidate is scored (per-pair hash noise), the rest
-        # of the step is the same.  One rank only: a citation graph's step is launch-bound, not something to shard.
+        # of the step is the same.  The WHOLE graph's candidates: on a row shard the step slices its rows' part once per graph
+        # (_cand_rows) and runs the row-range forms of the edge-list kernels with replicated features.  A citation graph's step is
+        # launch-bound (Pubmed: 0.29 ms fused on one GPU) and gains nothing from a shard; where larger edge lists stop being
+        # launch-bound has not been measured.
         self.cand = cand
         # scorer (edge-list candidates only): None = exp(t ||xp_i - xp_j||) (u-v-dist), or a dict with the edge-MLP scorer's terms in
         # the per-node / per-edge form of dgg_edge_mlp_fwd (reference dgm.py:1628-1719): Wcat [2hw,h], wdu / wdv / wex [hw] or None,
@@ -134,7 +147,8 @@ class ShardedDGGConv:
         self.coll = self.world > 1 or (dist.is_initialized() and os.environ.get("DGG_FORCE_COLLECTIVES") == "1")
         self.emulate = None
         self.r0, self.r1, self.per = shard_bounds(N, self.world, self.rank)
-        assert cand is None or self.world == 1, "edge-list candidates run on one rank"
+        assert cand is None or self.world == 1 or x_full is not None, "edge-list candidates on several ranks: replicated features (x_full)"
+        self._cand_cache = None                              # (rows, weakrefs of rowptr / col, their slice): _cand_rows
         self.bufs = {}                                       # collective staging buffers, kept between steps
         # Rows wider than the 64-rank list (all-pairs candidates, ranked noise): the learned degree is unbounded (dgm.py:1580-1584) and
         # the reference ramps over the whole dense row (dgm.py:1402-1421).  wide_rows: "off" = the [rows,64] list whatever k (exact
@@ -247,6 +261,20 @@ class ShardedDGGConv:
                 return None
         return kern.rowmin_logp_bound(xp, self.t, rows=(self.r0, self.r1))
 
+    def _cand_rows(self):
+        """-> (rowptr, col, (e0, e1)) of the rank's rows: the whole graph's own tensors when the rank holds every row, else the rebased
+        CSR slice (csr_rows), made on the device once per graph -- cached on the candidate tensors' identity (adjacency._cached keeps one
+        pair per graph object) -- so that a step reads nothing back"""
+        rowptr, col = self.cand
+        if (self.r0, self.r1) == (0, self.N):
+            return rowptr, col, (0, int(col.shape[0]))
+        ent = self._cand_cache
+        if ent is not None and ent[0] == (self.r0, self.r1) and ent[1]() is rowptr and ent[2]() is col:
+            return ent[3]
+        got = csr_rows(rowptr, col, (self.r0, self.r1))
+        self._cand_cache = ((self.r0, self.r1), weakref.ref(rowptr), weakref.ref(col), got)
+        return got
+
     def emulate_rank(self, world, rank):
         """TIMING DIAGNOSTIC (bench.py --emulate-world): do the work of `rank` of `world` in a single process -- own row range
         against all N columns, replicated features -- with the collectives left out and the other ranks' row sums faked by
@@ -321,25 +349,31 @@ class ShardedDGGConv:
             s["k"], s["z"], s["u"], s["feat"] = kern.knet_x_fwd(xk, deg_local, mu_sd, P["W1"], P["b1"], P["Wmu"], P["bmu"],
                                                               P["Wp"].reshape(-1), P["bp"])
         s["xp"] = xp = g_xp.get() if (self.coll and not repl) else xp
+        if self.cand is not None:
+            # a row shard: its rows' rebased CSR slice and the row-range entries (rows=); the whole graph: exactly the one-rank calls
+            rowptr, col, (e0, e1) = self._cand_rows()
+            rk = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
+            s["ncand"] = int(col.numel())
         if self.cand is not None and self.scorer is not None:
-            # edge-MLP scorer: first layer split into per-node products AB = xp [Wa | Wb]^T (MFMA GEMM) + per-edge terms
-            rowptr, col = self.cand
+            # edge-MLP scorer: first layer split into per-node products AB = xp [Wa | Wb]^T (MFMA GEMM, all N nodes) + per-edge terms
             sc = self.scorer
+            erow, ex_in = sc["erow"], sc["ex_in"]
+            if rk:                                  # (views: the shard's entries of the per-edge inputs)
+                erow, ex_in = erow[e0:e1], (None if ex_in is None else ex_in[e0:e1])
             s["AB"] = AB = kern.linear_fwd(xp, sc["Wcat"], None, 0, 0)
             s["sdeg"] = sdeg = deg_full if sc["wdu"] is not None else None
-            p_edge, s["ex"] = kern.edge_mlp_fwd(AB, xp, sc["erow"], col, sdeg, sc["ex_in"], sc["ex_mode"], sc["t_ex"], sc["wdu"], sc["wdv"],
+            p_edge, s["ex"] = kern.edge_mlp_fwd(AB, xp, erow, col, sdeg, ex_in, sc["ex_mode"], sc["t_ex"], sc["wdu"], sc["wdv"],
                                                 sc["wex"], sc["b1"], sc["w2"], sc["b2"], sc["act"])
-            s["idx"], s["val"], s["eid"] = kern.edgelist_topk_p(p_edge, self.N, rowptr, col, self.K, self.noise_mode, None, self.seed)
+            s["idx"], s["val"], s["eid"] = kern.edgelist_topk_p(p_edge, self.N, rowptr, col, self.K, self.noise_mode, None, self.seed, **rk)
             s["w"], rs_local = kern.softk_fwd(s["idx"], s["val"], s["k"], self.mode)
         elif self.cand is not None:
-            rowptr, col = self.cand
             # (self.overflow: optional int32[1] device flag the caller owns -- set when the K-wide list drops a weighted rank)
             got = kern.edgelist_topk_softk(xp, rowptr, col, s["k"], self.mode, self.K, self.t, self.noise_mode, None, self.seed,
-                                           overflow=getattr(self, "overflow", None)) if hasattr(kern, "edgelist_topk_softk") else None
+                                           overflow=getattr(self, "overflow", None), **rk) if hasattr(kern, "edgelist_topk_softk") else None
             if got is not None:                     # search + ramp in one launch
                 s["idx"], s["val"], s["w"], rs_local = got
             else:
-                s["idx"], s["val"] = kern.edgelist_topk(xp, rowptr, col, self.K, self.t, self.noise_mode, None, self.seed)
+                s["idx"], s["val"] = kern.edgelist_topk(xp, rowptr, col, self.K, self.t, self.noise_mode, None, self.seed, **rk)
                 s["w"], rs_local = kern.softk_fwd(s["idx"], s["val"], s["k"], self.mode)
         elif self.noise_mode == 4 and self.K == 64 and hasattr(kern, "allpairs_topk_softk") and xp.shape[1] in (8, 16, 32, 64, 128):
             # ranked noise: the ramp is applied inside the search kernel, while the settled list is still in registers
@@ -560,18 +594,22 @@ class ShardedDGGConv:
         return self._weight_grads(g, dxp, dH, dk, x_local, P)
 
     def _scorer_backward(self, g, dA, dH, da, x_local, P, cols_only=False):
-        """score backward of the edge-MLP scorer (one rank): ramp + normalisation backward by rows, the MLP's backward on the selected
+        """score backward of the edge-MLP scorer: ramp + normalisation backward by rows, the MLP's backward on the selected
         edges (dgg_edge_mlp_bwd: per-node dAB, parameter sums), AB's GEMM backward into dxp; the k-net and the fused weight gradients
         as for the distance scorer.  da [N]: d loss / d (rs^-1/2), both sides (dgg_norm_bwd_da), or with cols_only the neighbour-side
         sums (the row side is then formed inside the row kernel, dgg_softk_bwd_rows)."""
         kern, s, sc = self.kern, self.saved, self.scorer
+        if self.coll:                                   # (as in _backward: da summed over the ranks, dH's own rows reduce-scattered behind)
+            dist.all_reduce(da, group=self.group)
+        if self._hyb() and self.coll:
+            dH = self._reduce_scatter_rows(dH, "dH", async_op=True)
         if cols_only:
             dval, dk = kern.softk_bwd(s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.mode, True, ahat_rows=s["ahat"])
         else:
             dval, dk = kern.softk_bwd(s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.mode, True)
-        kw = {}
+        kw = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
         if s.get("partp") is not None and self.cand is not None and getattr(kern, "EMLP_BWD_PARTP", False):
-            kw = dict(partp=s["partp"], w=s["w"], nrec_max=int(self.cand[1].numel()))       # (a selected entry is a candidate edge)
+            kw.update(partp=s["partp"], w=s["w"], nrec_max=s["ncand"])       # (a selected entry is one of the rows' candidate edges)
         dAB, dpar, dex = kern.edge_mlp_bwd(s["AB"], s["idx"], s["eid"], s["val"], dval, s["sdeg"], s["ex"], sc["wdu"], sc["wdv"], sc["wex"],
                                            sc["b1"], sc["w2"], sc["b2"], sc["act"], self.noise_mode != 0, need_dex=sc["ex_mode"] == 2, **kw)
         dxp, dWcat, _ = kern.linear_bwd(s["xp"], sc["Wcat"], s["AB"], dAB, 0, 0, True, False)
@@ -649,17 +687,20 @@ class ShardedDGGConv:
             dX3, g["Wc"], _ = kern.linear_bwd(Xg, P["Wc"], None, dH_g, 0, 1, self.x_grad, False)
             dX2, g["Wk"], g["bk"] = kern.linear_bwd(x_local, P["Wk"], s["xk"], dxk, 1, 0, self.x_grad, True)
         if self.coll:
-            flat = _Gather._buf(self.bufs, ("wgrad", "flat"), (sum(int(g[k].numel()) for k in self.PARAM_KEYS),), g["We"])
+            # (the edge-MLP scorer's gradients -- g["scorer"], every rank's share of the selected edges -- ride in the same bucket)
+            sg = g.get("scorer")
+            parts = [(g, k) for k in self.PARAM_KEYS] + ([] if sg is None else [(sg, k) for k in sorted(sg) if sg[k] is not None])
+            flat = _Gather._buf(self.bufs, ("wgrad", "flat"), (sum(int(d_[k].numel()) for d_, k in parts),), g["We"])
             o = 0
-            for k in self.PARAM_KEYS:
-                n = g[k].numel()
-                flat[o:o + n].copy_(g[k].reshape(-1))
+            for d_, k in parts:
+                n = d_[k].numel()
+                flat[o:o + n].copy_(d_[k].reshape(-1))
                 o += n
             dist.all_reduce(flat, group=self.group)
             o = 0
-            for k in self.PARAM_KEYS:              # (copies: `flat` is a persistent bucket, overwritten by the next step's all-reduce)
-                n = g[k].numel()
-                g[k] = flat[o:o + n].view_as(g[k]).clone()
+            for d_, k in parts:                    # (copies: `flat` is a persistent bucket, overwritten by the next step's all-reduce)
+                n = d_[k].numel()
+                d_[k] = flat[o:o + n].view_as(d_[k]).clone()
                 o += n
         if self.x_grad:
             g["x"] = dX1 + dX3 + dX2                     # all three on the rank's own rows
