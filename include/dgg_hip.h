@@ -477,9 +477,15 @@ int dgg_partp_describe(int64_t rows, int K, int64_t ncols, int64_t *out6);
  * backward may then skip the row-major dA (dA = NULL in dgg_ell_conv_bwd_partp[_ext] and dgg_softk_edge_bwd_partp[_phase]) */
 int dgg_partp_has_map(int64_t rows);
 /* dgg_ell_conv_bwd_part on a payload partition (ahat_ir = record payload * rs_j^-1/2, bit-identical to dgg_ell_normalize_fwd);
- * also writes dA_rec [rows*K] = dA in record order.  dA, dH, da: caller zeroes.  dA may be NULL: the row-major copy (one scattered
- * 4-byte store per entry) is then not written, and dgg_softk_edge_bwd_partp -- called with dA = NULL as well -- reads dA_rec through the
- * slot -> record map the partition's sort leaves in its workspace. */
+ * also writes dA_rec [rows*K] = dA in record order (the first `number of records` positions; the rest is not written).
+ * Output contract (tests/test_partitioned_backward.py hands every output in filled with NaN):
+ *   dH [ncols,F], da [ncols]  one plain store per destination node, nodes without a record included (they receive 0): the caller
+ *                             need NOT zero them, nothing is accumulated into.  (rows == 0 launches nothing and writes nothing.)
+ *   dA [rows,K]               written on the ACTIVE entries (idx >= 0, w != 0) only; every other slot keeps what the caller put
+ *                             there -- zero it, or hand it to a consumer that masks those slots (dgg_softk_edge_bwd_partp with
+ *                             ahat_rows does).
+ * dA may be NULL: the row-major copy (one scattered 4-byte store per entry) is then not written, and dgg_softk_edge_bwd_partp -- called
+ * with dA = NULL as well -- reads dA_rec through the slot -> record map the partition's sort leaves in its workspace. */
 int dgg_ell_conv_bwd_partp(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
                            const float *rs, float *dA, float *dA_rec, float *dH, float *da, void *stream);
 /* the same when the normalised adjacency has OTHER consumers besides this aggregation (GCN_DGG hands it to its second layer as well,
@@ -490,7 +496,12 @@ int dgg_ell_conv_bwd_partp_ext(const float *G, const float *H, int64_t rows, int
 /* dgg_softk_edge_bwd_part on a payload partition: the column kernel recomputes d loss / d score (ramp + normalisation chain,
  * dgm.py:1410-1420, model.py:1215-1218) from dA_rec and the per-row scalars the row kernel leaves in rowinfo_ws (4*rows floats).
  * out_act = 1 (mode 0 only): dxp is returned multiplied by LeakyReLU'(xp) -- the gradient of the pre-activation of node_encode_for_edges
- * (dgm.py:1097-1100) -- so that the weight-gradient product needs no pass over xp for the mask. */
+ * (dgm.py:1097-1100) -- so that the weight-gradient product needs no pass over xp for the mask.
+ * Output contract: dk [rows] is written.  mode 0: EVERY row of dxp [ncols,h] receives a plain store -- rows [row0, row0 + rows) by the
+ * row kernel, then read, completed and stored again by the per-destination kernel; the other rows by the per-destination kernel alone
+ * -- so the caller need NOT zero dxp.  mode 1 (k_only: no gradient reaches the scores) runs the row kernel only: rows
+ * [row0, row0 + rows) of dxp receive zeros and the rows outside it are NOT written (the caller zeroes them).  With ahat_rows, slots
+ * of dA whose ahat is 0 are not read as values (they may hold anything, NaN included). */
 int dgg_softk_edge_bwd_partp(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
                              const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
                              int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,

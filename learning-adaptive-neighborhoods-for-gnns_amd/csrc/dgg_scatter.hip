@@ -1763,7 +1763,8 @@ static bool node_groups(int64_t nrec, int64_t ncols) {
 }
 
 // dgg_ell_conv_bwd_part on a payload partition: ahat comes from the records; additionally dA_rec [rows*K] = dA in record order
-// (for dgg_softk_edge_bwd_partp).  dA [rows,K], dH [ncols,F], da [ncols] as in dgg_ell_conv_bwd_part (caller zeroes all three).
+// (for dgg_softk_edge_bwd_partp).  dH [ncols,F] and da [ncols]: one plain store per destination node (no zero fill by the caller);
+// dA [rows,K]: written on the active entries only (see include/dgg_hip.h).
 int dgg_ell_conv_bwd_partp_ext(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
                                const float *rs, const float *dA_ext, float *dA, float *dA_rec, float *dH, float *da, void *stream);
 int dgg_ell_conv_bwd_partp(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
@@ -1812,7 +1813,8 @@ int dgg_softk_edge_bwd_partp_phase(const float *xp, int64_t rows, int h, const i
                                    float *dxp, int out_act, int phase, void *stream);
 // dgg_softk_edge_bwd_part on a payload partition: the row kernel hands (a_i, d loss / d rs_i, k_i) per row to the column kernel
 // (rowinfo_ws: 4*rows floats), which recomputes d loss / d score from dA_rec in record order -- no slot map, no per-entry
-// coefficient hand-over.  dk [rows] written, dxp [ncols,h] zeroed by the caller.
+// coefficient hand-over.  dk [rows] written; dxp [ncols,h]: mode 0 stores every row (no zero fill by the caller), mode 1 only the
+// rows of the block (see include/dgg_hip.h).
 int dgg_softk_edge_bwd_partp(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
                              const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
                              int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
