@@ -365,6 +365,14 @@ int dgg_csr_rank_cut_bwd(const int32_t *pos, const float *g, int64_t E, int kcut
 int dgg_csr_uvdist_fwd(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t N, int h, float t, float *p, void *stream);
 int dgg_csr_uvdist_bwd(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t N, int h, float t, const float *p,
                        const float *dp, float *dxp, void *stream);
+/* the same variants with perturb_edge_prob (debug_step 1 / `edge_p-cdf`): the perturbation of dgm.py:1211-1229 on the stored entries,
+ * q_e = exp(log(p_e + 1e-8) + G_e), one rounding per step -- the bits the top-k searches rank under the same noise.  erow / col [E]:
+ * row and column of every entry (both < N); noise_mode DGG_NOISE_EXPLICIT (G [N, ldG]) / HASH / HASH_SYM (asymmetric diagonal
+ * perturbed, symmetric diagonal 0, as in the reference).  The reference's non-edges (1e-8 exp(G) <= ~3e-7) are not produced.
+ * Backward (dgm.py:1211-1229 differentiated): dp_e = dq_e q_e / (p_e + 1e-8) from the saved p and q; no noise is read. */
+int dgg_csr_perturb_fwd(const float *p, const int32_t *erow, const int32_t *col, int64_t E, int64_t N, int noise_mode, const float *G,
+                        int64_t ldG, uint32_t s0, uint32_t s1, float *q, void *stream);
+int dgg_csr_perturb_bwd(const float *p, const float *q, const float *dq, int64_t E, float *dp, void *stream);
 /* normalize_adj of the *_DGG_00 wrappers (model.py:1340-1352): rs = row sums, ahat_e = rs_i^-1/2 w_e rs_j^-1/2 */
 int dgg_csr_row_sum(const float *vals, const int64_t *rowptr, int64_t N, float *rs, void *stream);
 int dgg_csr_normalize_fwd(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, int64_t N, float *ahat,

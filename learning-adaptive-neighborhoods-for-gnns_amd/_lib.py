@@ -81,6 +81,8 @@ PROTOTYPES = {
     "dgg_feat_softmax_bwd": [_vp, _vp, _i64, _i32, _vp, _vp],
     "dgg_csr_uvdist_fwd": [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp],
     "dgg_csr_uvdist_bwd": [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp],
+    "dgg_csr_perturb_fwd": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _u32, _u32, _vp, _vp],
+    "dgg_csr_perturb_bwd": [_vp, _vp, _vp, _i64, _vp, _vp],
     "dgg_csr_row_sum": [_vp, _vp, _i64, _vp, _vp],
     "dgg_csr_normalize_fwd": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "dgg_csr_norm_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],

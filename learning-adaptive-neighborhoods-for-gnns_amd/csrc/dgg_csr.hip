@@ -340,6 +340,27 @@ __global__ __launch_bounds__(WPB * 64) void csr_uvdist_bwd_kernel(const float *_
     }
 }
 
+// ---- perturbed edge probabilities as the adjacency (debug_step 1 / edge_p-cdf with perturb_edge_prob, dgm.py:1211-1229) ---------
+// q_e = exp(log(p_e + 1e-8) + G_e) on the stored entries: score_from_dist's perturb branch, one rounding per step, so q_e carries
+// the bits the top-k searches rank under the same noise.  Lane = entry (row from erow, no row walk); streaming, ~16 B per entry.
+// The reference's non-edges (1e-8 exp(G), at most ~3e-7) are dropped like those of the perturbed k_times_edge_prob path.
+__global__ __launch_bounds__(256) void csr_perturb_fwd_kernel(const float *__restrict__ p, const int32_t *__restrict__ erow,
+                                                            const int32_t *__restrict__ col, int64_t E, int noise_mode,
+                                                            const float *__restrict__ G, int64_t ldG, uint32_t s0, uint32_t s1,
+                                                            float *__restrict__ q) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int32_t i = erow[e], j = col[e];
+    const float g = noise_mode == 1 ? G[(int64_t)i * ldG + j] : pair_noise(s0, s1, (uint32_t)i, (uint32_t)j, noise_mode == 3);
+    q[e] = c_exp(__fadd_rn(c_log(__fadd_rn(p[e], 1e-8f)), g));
+}
+// dp_e = dq_e q_e / (p_e + 1e-8) (= dq_e exp(G_e)): from the saved p and q, no noise read, no generator
+__global__ __launch_bounds__(256) void csr_perturb_bwd_kernel(const float *__restrict__ p, const float *__restrict__ q,
+                                                            const float *__restrict__ dq, int64_t E, float *__restrict__ dp) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < E) dp[e] = __fdiv_rn(__fmul_rn(dq[e], q[e]), __fadd_rn(p[e], 1e-8f));
+}
+
 // ---- GATConv_DGG (reference model.py:534-577): row softmax with a uniform background ---------------------------------
 // The reference builds a dense [N,N] logit matrix: e_ij on the entries of edge_index, -1e20 elsewhere, multiplied by the
 // dense learned adjacency.  Every pair that is in neither list gets logit -1e20 * 0 = -0, i.e. exp(0) = 1 in the softmax:
@@ -511,6 +532,27 @@ int dgg_csr_softk_bwd(const float *p, const float *pp, const int64_t *rowptr, in
     hipLaunchKernelGGL(csr_softk_bwd_kernel, dim3((unsigned)((N + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, p, pp, rowptr, N, k,
                        pos, perturb, mode, g, dp, dk);
     return dgg_check_launch("csr_softk_bwd");
+}
+
+// perturbed edge probabilities on the stored entries (dgm.py:1211-1229): p [E], erow / col [E] (row and column of every entry, both
+// < N), noise_mode 1 explicit G [N, ldG] / 2 hash / 3 symmetric hash -> q [E].  E == 0 launches nothing.
+int dgg_csr_perturb_fwd(const float *p, const int32_t *erow, const int32_t *col, int64_t E, int64_t N, int noise_mode, const float *G,
+                        int64_t ldG, uint32_t s0, uint32_t s1, float *q, void *stream) {
+    if (noise_mode < 1 || noise_mode > 3 || (noise_mode == 1 && (!G || ldG < N)))
+        return dgg_set_error(DGG_ERR_ARG, "csr_perturb_fwd: noise_mode 1 (explicit, G [N, ldG >= N]), 2 (hash) or 3 (symmetric hash)");
+    if (E < 0 || N < 0 || N > 0x7fffffffll || (E + 255) / 256 > 0x7fffffffll)
+        return dgg_set_error(DGG_ERR_ARG, "csr_perturb_fwd: sizes out of range");
+    if (E == 0) return 0;
+    hipLaunchKernelGGL(csr_perturb_fwd_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, erow, col, E,
+                       noise_mode, G, ldG, s0, s1, q);
+    return dgg_check_launch("csr_perturb_fwd");
+}
+// dp_e = dq_e q_e / (p_e + 1e-8) from the saved p and q
+int dgg_csr_perturb_bwd(const float *p, const float *q, const float *dq, int64_t E, float *dp, void *stream) {
+    if (E < 0 || (E + 255) / 256 > 0x7fffffffll) return dgg_set_error(DGG_ERR_ARG, "csr_perturb_bwd: sizes out of range");
+    if (E == 0) return 0;
+    hipLaunchKernelGGL(csr_perturb_bwd_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, q, dq, E, dp);
+    return dgg_check_launch("csr_perturb_bwd");
 }
 
 int dgg_csr_rank_ramp_fwd(const float *p, const int64_t *rowptr, const int32_t *col, int64_t N, const float *w, const float *b,

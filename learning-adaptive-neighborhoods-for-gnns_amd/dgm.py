@@ -1073,14 +1073,15 @@ class DGG_LearnableK_debug(nn.Module):
     def _scores_adjacency(self, x, in_adj):
         """debug_step 0 (dgm.py:1202-1209), debug_step 1 (dgm.py:1240-1246) and k-select `edge_p-cdf` (dgm.py:1368-1401, whose
         scatter puts the UNSORTED probabilities back and whose learned k never reaches the output): the adjacency IS the edge
-        probability of every stored entry of in_adj -> CsrAdjacency on its pattern.  Perturbed probabilities (debug_step 1 /
-        edge_p-cdf with perturb_edge_prob) are dense in the reference (every non-edge becomes 1e-8 exp(G) > 0) and are not
-        produced; dgg_hard turns these outputs into all-ones matrices there (dgm.py:1301-1306 with idxs=None)."""
+        probability of every stored entry of in_adj -> CsrAdjacency on its pattern.  With perturb_edge_prob, debug_step 1 and
+        edge_p-cdf return the PERTURBED probabilities (dgm.py:1211-1229; debug_step 0 returns before the perturbation): the stored
+        entries carry (p + 1e-8) exp(G) (ops.CsrPerturbFn, noise from _noise_cfg like every other forward), the bits the top-k
+        searches rank under the same noise.  The reference's result is dense there -- every non-edge becomes 1e-8 exp(G), at most
+        ~3e-7 -- and those entries are dropped, as on the perturbed k_times_edge_prob path (DESIGN.md "Deviations").  The learned k
+        and signal_project never reach the output of edge_p-cdf and get no gradient.  dgg_hard turns these outputs into all-ones
+        matrices in the reference (dgm.py:1301-1306 with idxs=None)."""
         if self.hard:
             raise NotImplementedError("dgg_hard with debug_step 0/1 or edge_p-cdf is a dense all-ones matrix in the reference")
-        if self.args.perturb_edge_prob and self.args.debug_step != 0:
-            raise NotImplementedError("perturbed edge probabilities are returned as a DENSE [N,N] matrix by the reference "
-                                      "(debug_step 1 / edge_p-cdf with perturb_edge_prob=True)")
         if isinstance(in_adj, AllPairs):
             raise NotImplementedError("all-pairs candidates: the raw probability matrix is dense [N,N]")
         if isinstance(in_adj, (EllAdjacency, CsrAdjacency)):
@@ -1097,6 +1098,9 @@ class DGG_LearnableK_debug(nn.Module):
             cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
             p = _DGGScoresFn.apply(x, deg, ex_in, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"], mlp["w2"],
                                    mlp["b2"], cfg)
+        if self.args.perturb_edge_prob and self.args.debug_step != 0:
+            noise_mode, G, seed = self._noise_cfg()
+            p = ops.CsrPerturbFn.apply(p, pattern[0], pattern[1], pattern[2], x.shape[0], noise_mode, G, seed)
         return CsrAdjacency(pattern[0], pattern[1], pattern[2], p, x.shape[0])
 
     def forward(self, x, in_adj, noise=True, writer=None, epoch=None):

@@ -932,6 +932,56 @@ def csr_uvdist_bwd(xp, rowptr, col, p, dp, t=T_DIST):
     return dxp
 
 
+def _hash_noise_mode(noise_mode):
+    """the ranked generators serve all-pairs rows only: stored entries take the per-pair hash of the same law"""
+    return {NOISE_RANKED: NOISE_HASH, NOISE_RANKED_SYM: NOISE_HASH_SYM}.get(noise_mode, noise_mode)
+
+
+def csr_perturb_fwd(p, erow, col, N, noise_mode, G=None, seed=(0, 0)):
+    """dgm.py:1211-1229 on the stored entries: q_e = exp(log(p_e + 1e-8) + G[erow_e, col_e]) -> [E]; noise_mode NOISE_EXPLICIT
+    (G [N,N]), NOISE_HASH / NOISE_HASH_SYM (seed; the ranked modes map to them)"""
+    p = _chk(p)
+    erow, col = _chk(erow, torch.int32), _chk(col, torch.int32)
+    assert erow.shape == col.shape == p.shape, "csr_perturb_fwd: p, erow, col [E]"
+    noise_mode = _hash_noise_mode(noise_mode)
+    ldG = 0
+    if noise_mode == NOISE_EXPLICIT:
+        G = _chk(G)
+        assert G.ndim == 2 and G.shape[0] >= N, "csr_perturb_fwd: explicit noise is a dense [N,N] tensor"
+        ldG = G.shape[-1]
+    else:
+        G = None
+    q = torch.empty_like(p)
+    _lib.check(_lib.lib().dgg_csr_perturb_fwd(_ptr(p), _ptr(erow), _ptr(col), p.numel(), int(N), noise_mode, _ptr(G), ldG, seed[0], seed[1],
+                                              _ptr(q), _stream()), "csr_perturb_fwd")
+    return q
+
+
+def csr_perturb_bwd(p, q, dq):
+    """dp_e = dq_e q_e / (p_e + 1e-8)"""
+    p = _chk(p)
+    dp = torch.empty_like(p)
+    _lib.check(_lib.lib().dgg_csr_perturb_bwd(_ptr(p), _ptr(_chk(q)), _ptr(_chk(dq)), p.numel(), _ptr(dp), _stream()), "csr_perturb_bwd")
+    return dp
+
+
+class CsrPerturbFn(torch.autograd.Function):
+    """perturbed edge probabilities on the CSR pattern (debug_step 1 / edge_p-cdf with perturb_edge_prob, dgm.py:1211-1229):
+    p [E] -> q [E]"""
+
+    @staticmethod
+    def forward(ctx, p, rowptr, col, erow, N, noise_mode, G, seed):
+        p = _chk(p)
+        q = csr_perturb_fwd(p, erow, col, N, noise_mode, G, seed)
+        ctx.save_for_backward(p, q)
+        return q
+
+    @staticmethod
+    def backward(ctx, dq):
+        p, q = ctx.saved_tensors
+        return (csr_perturb_bwd(p, q, dq.contiguous()),) + (None,) * 7
+
+
 def csr_row_sum(vals, rowptr):
     N = rowptr.shape[0] - 1
     rs = torch.empty((N,), device=vals.device, dtype=torch.float32)
