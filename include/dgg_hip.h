@@ -330,23 +330,34 @@ int dgg_edge_mlp_bwd_partp_rows(const float *AB, int64_t N, int hw, int64_t row0
 /* ---- CSR-valued adjacency (variable row length) + the `DGG` class "for ICLR" (dgm.py:1730-1815) ---------------------
  * `DGG.forward` keeps every candidate edge (weight rank * (ramp + 1), dgm.py:1804-1807), so its output has the sparsity
  * of in_adj (rows up to 168 wide on Cora) and is carried as values [E] on the CSR pattern (rowptr int64 [N+1], col
- * int32 [E], columns of a row ascending).  dgg_edge_mlp_bwd takes the same pattern through its rowptr argument. */
+ * int32 [E], columns of a row ascending).  dgg_edge_mlp_bwd takes the same pattern through its rowptr argument.
+ * Writes of this family (held by tests/test_csr_adjacency.py): an output [E] is OVERWRITTEN on every stored entry, an output [N] on
+ * every row, empty rows included; nothing is written beyond word E / row N, and N == 0 (E == 0 for the entry-wise functions)
+ * returns 0 without a launch.  The three outputs that are ACCUMULATED into say so below.  Offsets are 64-bit.
+ * Ranking (dgg_csr_rank_ramp_fwd, dgg_csr_softk_fwd, dgg_csr_rank_cut_fwd) orders a row by the BIT PATTERN of the value (then the
+ * lower column), which is the float order only for non-negative values without -0.0: the ranked values must be >= +0.0 (NaN and
+ * -0.0 excluded).  Every caller passes a sigmoid or exp output (dgm.py: edge_mlp_fwd's sigmoid, csr_noisy_sigmoid_fwd, the u-v-dist
+ * exp; dgg_csr_softk_fwd ranks p' = exp(.) or, without noise, that p itself). */
 /* dgm.py:1791-1812: S_i = sum_j rank_ij; k_i = degree_decoder(S_i) = leaky(S_i w + b) (w, b device pointers);
  * pos_e = rank position of edge e in its row under torch.sort(descending) (ties: lower column first);
  * out_e = rank_e * ((1 - 0.5 (1 + tanh(pos_e - k_i))) + 1) */
 int dgg_csr_rank_ramp_fwd(const float *p, const int64_t *rowptr, const int32_t *col, int64_t N, const float *w, const float *b,
                           float *out, float *S, float *k, int32_t *pos, void *stream);
-/* g = d loss / d out -> dp [E] (direct + through S -> k), dkz [N] = d loss / d (S_i w + b) (dw = <dkz, S>, db = sum dkz) */
+/* g = d loss / d out -> dp [E] (direct + through S -> k), dkz [N] = d loss / d (S_i w + b) (dw = <dkz, S>, db = sum dkz); both
+ * overwritten (dkz of an empty row: 0) */
 int dgg_csr_rank_ramp_bwd(const float *p, const int64_t *rowptr, int64_t N, const float *w, const float *b, const float *S,
                           const float *k, const int32_t *pos, const float *g, float *dp, float *dkz, void *stream);
 /* select_top_k of DGG_LearnableK_debug (dgm.py:1402-1435) on rows of ANY width: the CSR counterpart of dgg_edgelist_topk_p +
  * dgg_softk_fwd for graphs whose rows have more candidates than the ELL width and whose learned degrees may exceed it.
  * p [E] edge probabilities (edge_prob_net, dgm.py:1607-1725), k [N]; noise_mode DGG_NOISE_NONE / EXPLICIT (G [N, ldG]) / HASH / HASH_SYM
  * (dgm.py:1213-1229); mode 0 k_times_edge_prob, 1 k_only.  -> w [E] = p' * ramp(pos - k) (mode 0) or the ramp, pp [E] = p', pos [E]
- * = position of the entry in its row's descending sort (ties: lower column first). */
+ * = position of the entry in its row's descending sort (ties: lower column first).  w, pp, pos overwritten on every entry.  Explicit noise
+ * is read at G[i * ldG + j] for the stored pairs only (ldG >= N; padding columns are never read).  DGG_ERR_ARG and nothing written for a
+ * noise_mode outside 0..3, DGG_NOISE_EXPLICIT without G, or a mode other than 0 / 1. */
 int dgg_csr_softk_fwd(const float *p, const int64_t *rowptr, const int32_t *col, int64_t N, const float *k, int noise_mode, const float *G,
                       int64_t ldG, uint32_t s0, uint32_t s1, int mode, float *w, float *pp, int32_t *pos, void *stream);
-/* g = d loss / d w -> dp [E] (through the perturbation when perturb != 0), dk [N] */
+/* g = d loss / d w -> dp [E] (through the perturbation when perturb != 0: times pp / (p + 1e-8); exactly 0 in mode 1), dk [N]; both
+ * overwritten */
 int dgg_csr_softk_bwd(const float *p, const float *pp, const int64_t *rowptr, int64_t N, const float *k, const int32_t *pos, int perturb,
                       int mode, const float *g, float *dp, float *dk, void *stream);
 /* `DGG_Ablations.forward` (dgm.py:1927-1962): edge_rank = sigmoid(sigmoid(score) + noise), noise ~ U(-1,1) per stored edge
@@ -355,13 +366,16 @@ int dgg_csr_noisy_sigmoid_fwd(const float *p, const float *noise, int64_t E, flo
 /* dp_e = g_e out_e (1 - out_e) */
 int dgg_csr_noisy_sigmoid_bwd(const float *out, const float *g, int64_t E, float *dp, void *stream);
 /* fixed k (dgm.py:1940-1942, `srt_edge_rank[:, k:] = 0`): out_e = p_e if fewer than kcut entries of the row sort before e
- * under (rank desc, column asc), else 0; pos as in dgg_csr_rank_ramp_fwd */
+ * under (rank desc, column asc), else 0; pos as in dgg_csr_rank_ramp_fwd.  kcut < 0: DGG_ERR_ARG, nothing written */
 int dgg_csr_rank_cut_fwd(const float *p, const int64_t *rowptr, const int32_t *col, int64_t N, int kcut, float *out, int32_t *pos,
                          void *stream);
 int dgg_csr_rank_cut_bwd(const int32_t *pos, const float *g, int64_t E, int kcut, float *dp, void *stream);
 /* raw edge probabilities as the adjacency -- debug_step 0/1 (dgm.py:1202-1209, 1240-1246) and k-select mode `edge_p-cdf`
  * (dgm.py:1368-1401 scatters the unsorted probabilities back) of DGG_LearnableK_debug.  u-v-dist scorer on the stored
- * entries (dgm.py:1613-1627): p_e = exp(t ||xp_u - xp_v||); backward: dxp [N,h] accumulated (caller zeroes) */
+ * entries (dgm.py:1613-1627): p_e = exp(t ||xp_u - xp_v||), p overwritten on every entry; h < 1: DGG_ERR_ARG, nothing written.
+ * Backward: dxp [N,h] is ACCUMULATED into (float atomics: rows i and col_e of every entry with dp_e p_e t != 0 and a non-zero
+ * distance receive +- the term); it must hold the caller's start value (zeros for the plain gradient).  An entry at zero distance (a
+ * self loop, identical rows) contributes exactly 0, never NaN; rows of nodes that no such entry touches keep their bits. */
 int dgg_csr_uvdist_fwd(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t N, int h, float t, float *p, void *stream);
 int dgg_csr_uvdist_bwd(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t N, int h, float t, const float *p,
                        const float *dp, float *dxp, void *stream);
@@ -373,21 +387,30 @@ int dgg_csr_uvdist_bwd(const float *xp, const int64_t *rowptr, const int32_t *co
 int dgg_csr_perturb_fwd(const float *p, const int32_t *erow, const int32_t *col, int64_t E, int64_t N, int noise_mode, const float *G,
                         int64_t ldG, uint32_t s0, uint32_t s1, float *q, void *stream);
 int dgg_csr_perturb_bwd(const float *p, const float *q, const float *dq, int64_t E, float *dp, void *stream);
-/* normalize_adj of the *_DGG_00 wrappers (model.py:1340-1352): rs = row sums, ahat_e = rs_i^-1/2 w_e rs_j^-1/2 */
+/* normalize_adj of the *_DGG_00 wrappers (model.py:1340-1352): rs = row sums (overwritten on every row, 0 for an empty row),
+ * ahat_e = rs_i^-1/2 w_e rs_j^-1/2 (overwritten on every entry).  Precondition of dgg_csr_normalize_fwd / dgg_csr_norm_bwd: rs must be
+ * positive on every node a stored entry names, as its row or as its column (an empty row may have rs = 0 as long as nobody lists it);
+ * an entry that names a node with rs = 0 comes out Inf or NaN. */
 int dgg_csr_row_sum(const float *vals, const int64_t *rowptr, int64_t N, float *rs, void *stream);
 int dgg_csr_normalize_fwd(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, int64_t N, float *ahat,
                           void *stream);
-/* autograd of the two: dA (wrt ahat) -> dw; da_ws [N] zeroed by the caller */
+/* autograd of the two: dA (wrt ahat) -> dw [E], overwritten.  da_ws [N] is a workspace that MUST BE ZERO ON ENTRY: the first kernel
+ * accumulates d loss / d rs_i^-1/2 into it (float atomics), the second reads it back into dw -- whatever it held on entry enters dw. */
 int dgg_csr_norm_bwd(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, const float *dA, int64_t N,
                      float *da_ws, float *dw, void *stream);
-/* torch.mm(adj, x) (model.py:594) on the CSR pattern and its autograd (dA [E]; dX nullable, accumulated into) */
+/* torch.mm(adj, x) (model.py:594) on the CSR pattern: Y [N,F] overwritten on every row (an empty row: zeros); N == 0 or F == 0
+ * returns 0.  Its autograd: dA [E] overwritten, the same bits with dX == NULL; dX [N,F] (nullable) is ACCUMULATED into (float atomics
+ * on row col_e of every entry with a_e != 0): it must hold the caller's start value (zeros for the plain gradient); rows of nodes
+ * that no entry with a_e != 0 lists keep their bits. */
 int dgg_csr_spmm_fwd(const int64_t *rowptr, const int32_t *col, const float *a, const float *X, int64_t N, int F, float *Y,
                      void *stream);
 int dgg_csr_spmm_bwd(const int64_t *rowptr, const int32_t *col, const float *a, const float *X, const float *dY, int64_t N, int F,
                      float *dA, float *dX, void *stream);
 /* GATConv_DGG (model.py:534-577): softmax(dim=1) of the dense logit matrix whose explicit entries are L [E] on the CSR
  * pattern and whose other N - cnt_i entries per row are the logit 0 that -1e20 * 0 produces (model.py:565-567):
- * att [E] on the pattern, bg [N] = the weight every non-listed node of a row receives.  Backward: datt, dbg -> dL. */
+ * att [E] on the pattern, bg [N] = the weight every non-listed node of a row receives; both overwritten.  A row that lists all N
+ * columns has bg = 0 exactly, a row without entry bg = 1/N.  exp is the fast hardware form (exp2 of a float32 product with log2 e):
+ * the relative error of a weight grows with |L - max| 2^-24.  Backward: datt, dbg -> dL [E], overwritten. */
 int dgg_csr_bg_softmax_fwd(const float *L, const int64_t *rowptr, int64_t N, float *att, float *bg, void *stream);
 int dgg_csr_bg_softmax_bwd(const float *att, const float *bg, const int64_t *rowptr, int64_t N, const float *datt, const float *dbg,
                            float *dL, void *stream);
@@ -395,7 +418,9 @@ int dgg_csr_bg_softmax_bwd(const float *att, const float *bg, const int64_t *row
  * with probability 1 - p -- the non-listed pairs, which all carry bg_i, included.  The mask is counter-based (pair (i, j) kept iff
  * hash24(s0, s1 ^ 0x9E3779B9 (i + 1), j) >= p 2^24; the reference draws from torch's generator: same law, another realisation), so
  * no N x N tensor exists: out_r = sum_s keep(r, s) X_s (transpose 0; the forward's sum of the kept rows of h) or sum_s keep(s, r) X_s
- * (transpose 1; its backward).  X, out [N,F], F <= 64.  dgg_pair_keep: the same mask on listed pairs (erow, col) [E] -> 1.0 / 0.0. */
+ * (transpose 1; its backward).  X, out [N,F], F <= 64; out overwritten on every row.  dgg_pair_keep: the same mask on listed pairs
+ * (erow, col) [E] -> 1.0 / 0.0.  p is taken as a float32: the threshold is (uint32)(p 2^24) of THAT value.  F outside [1,64] or p outside
+ * [0,1): DGG_ERR_UNSUPPORTED (dgg_pair_keep: DGG_ERR_ARG), nothing written. */
 int dgg_masked_dense_sum(const float *X, int64_t N, int F, float p, uint32_t s0, uint32_t s1, int transpose, float *out, void *stream);
 int dgg_pair_keep(const int32_t *erow, const int32_t *col, int64_t E, float p, uint32_t s0, uint32_t s1, float *out, void *stream);
 /* selection only, from a dense score matrix [R,N] (test entry: torch.sort(pert_edge_p)[:, :K], dgm.py:1404) */

@@ -311,7 +311,7 @@ __global__ __launch_bounds__(WPB * 64) void csr_uvdist_fwd_kernel(const float *_
         p[e] = c_exp(__fmul_rn(t, d));
     }
 }
-// dp -> dxp (accumulated, caller zeroes): lane = feature, entries of the row in sequence; own row by plain accumulation in
+// dp -> dxp (accumulated onto the caller's start value): lane = feature, entries of the row in sequence; own row by plain accumulation in
 // registers, neighbour rows by float atomics (edge lists are small: the 100k-node path never comes here)
 __global__ __launch_bounds__(WPB * 64) void csr_uvdist_bwd_kernel(const float *__restrict__ xp, const int64_t *__restrict__ rowptr,
                                                                  const int32_t *__restrict__ col, int64_t N, int h, float t,
@@ -495,7 +495,7 @@ int dgg_csr_spmm_fwd(const int64_t *rowptr, const int32_t *col, const float *a, 
     return dgg_check_launch("csr_spmm_fwd");
 }
 
-// dA [E] overwritten; dX (nullable, [N,F]) accumulated into (caller zeroes)
+// dA [E] overwritten; dX (nullable, [N,F]) accumulated into: it holds the caller's start value (zeros for the plain gradient)
 int dgg_csr_spmm_bwd(const int64_t *rowptr, const int32_t *col, const float *a, const float *X, const float *dY, int64_t N, int F,
                      float *dA, float *dX, void *stream) {
     if (N == 0) return 0;
@@ -504,7 +504,7 @@ int dgg_csr_spmm_bwd(const int64_t *rowptr, const int32_t *col, const float *a, 
     return dgg_check_launch("csr_spmm_bwd");
 }
 
-// da_ws [N] zeroed by the caller; dw [E] overwritten
+// da_ws [N] must be zero on entry (accumulated into, then read back into dw); dw [E] overwritten
 int dgg_csr_norm_bwd(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, const float *dA, int64_t N,
                      float *da_ws, float *dw, void *stream) {
     if (N == 0) return 0;
