@@ -360,6 +360,21 @@ int dgg_csr_softk_fwd(const float *p, const int64_t *rowptr, const int32_t *col,
  * overwritten */
 int dgg_csr_softk_bwd(const float *p, const float *pp, const int64_t *rowptr, int64_t N, const float *k, const int32_t *pos, int perturb,
                       int mode, const float *g, float *dp, float *dk, void *stream);
+/* ROW-RANGE FORMS (suffix _rows; held by tests/test_csr_row_shards.py): a row shard owns rows [row0, row0 + n) of a pattern over N nodes
+ * and passes them as a rectangular slice -- rowptr int64 [n+1] REBASED to start at 0, col int32 [E_loc] with GLOBAL column ids < N,
+ * per-entry arrays [E_loc], per-row arrays [n], per-node tables (xp, rs, da_ws, dxp) of the full length N.  Local row i is node
+ * row0 + i: that id, not i, indexes the tables and keys the noise.  On every range an overwritten output equals, bit for bit, the
+ * matching slice of the full-graph entry, which is the row0 = 0, n = N case of the same device code.  Every _rows entry returns
+ * DGG_ERR_ARG and writes nothing unless 0 <= row0 <= row0 + n <= N < 2^31; n == 0 returns 0 without a launch.
+ * Entries in which no row index reaches a table or a hash, and N is only a row count, take a slice through their EXISTING entry with
+ * N = n: dgg_csr_softk_bwd (k, dk [n]), dgg_csr_row_sum (rs [n]), dgg_csr_spmm_fwd / dgg_csr_spmm_bwd (Y, dY [n,F]; X, dX of every
+ * node the columns name).  dgg_edge_mlp_bwd has its row-range form already: dgg_edge_mlp_bwd_rows with the slice's rowptr.
+ * dgg_csr_softk_fwd_rows: as dgg_csr_softk_fwd with k [n]; noise_mode DGG_NOISE_NONE / HASH / HASH_SYM, the hash keyed on the global pair
+ * (row0 + i, col), so the realisation does not depend on the split and symmetric noise stays symmetric across a shard boundary; w, pp,
+ * pos [E_loc] overwritten on every entry.  DGG_ERR_ARG and nothing written for DGG_NOISE_EXPLICIT (a G [N, ldG] is not sliced) or any other
+ * noise_mode, or a mode other than 0 / 1. */
+int dgg_csr_softk_fwd_rows(const float *p, const int64_t *rowptr, const int32_t *col, int64_t row0, int64_t n, int64_t N, const float *k,
+                           int noise_mode, uint32_t s0, uint32_t s1, int mode, float *w, float *pp, int32_t *pos, void *stream);
 /* `DGG_Ablations.forward` (dgm.py:1927-1962): edge_rank = sigmoid(sigmoid(score) + noise), noise ~ U(-1,1) per stored edge
  * (dgm.py:1930-1933; the caller draws the noise); out [E] */
 int dgg_csr_noisy_sigmoid_fwd(const float *p, const float *noise, int64_t E, float *out, void *stream);
@@ -379,6 +394,14 @@ int dgg_csr_rank_cut_bwd(const int32_t *pos, const float *g, int64_t E, int kcut
 int dgg_csr_uvdist_fwd(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t N, int h, float t, float *p, void *stream);
 int dgg_csr_uvdist_bwd(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t N, int h, float t, const float *p,
                        const float *dp, float *dxp, void *stream);
+/* row-range forms (see dgg_csr_softk_fwd_rows): xp [N,h] every node's, read at row0 + i for the row and at col_e for the column;
+ * p [E_loc] overwritten on every entry; h < 1: DGG_ERR_ARG, nothing written.  Backward: dxp [N,h] is ACCUMULATED into at rows row0 + i
+ * and col_e under the conditions of dgg_csr_uvdist_bwd; it must hold the caller's start value (zeros, or the shares other slices
+ * already added: the slices of a partition, accumulated into one buffer, give the full-graph gradient). */
+int dgg_csr_uvdist_fwd_rows(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t row0, int64_t n, int64_t N, int h, float t,
+                            float *p, void *stream);
+int dgg_csr_uvdist_bwd_rows(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t row0, int64_t n, int64_t N, int h, float t,
+                            const float *p, const float *dp, float *dxp, void *stream);
 /* the same variants with perturb_edge_prob (debug_step 1 / `edge_p-cdf`): the perturbation of dgm.py:1211-1229 on the stored entries,
  * q_e = exp(log(p_e + 1e-8) + G_e), one rounding per step -- the bits the top-k searches rank under the same noise.  erow / col [E]:
  * row and column of every entry (both < N); noise_mode DGG_NOISE_EXPLICIT (G [N, ldG]) / HASH / HASH_SYM (asymmetric diagonal
@@ -398,6 +421,21 @@ int dgg_csr_normalize_fwd(const int64_t *rowptr, const int32_t *col, const float
  * accumulates d loss / d rs_i^-1/2 into it (float atomics), the second reads it back into dw -- whatever it held on entry enters dw. */
 int dgg_csr_norm_bwd(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, const float *dA, int64_t N,
                      float *da_ws, float *dw, void *stream);
+/* row-range forms (see dgg_csr_softk_fwd_rows).  dgg_csr_row_sum and dgg_csr_spmm_fwd / _bwd accept rectangular slices as they are (N = n:
+ * their row index reaches only rowptr and the per-row output; columns index X / dX, which hold every node the columns name).
+ * dgg_csr_normalize_fwd_rows: rs [N] the row sums of EVERY node (a shard gathers the other shards' first), read at row0 + i and col_e under
+ * the precondition of dgg_csr_normalize_fwd; ahat [E_loc] overwritten on every entry.
+ * The backward is dgg_csr_norm_bwd's two kernels as two entries, for a caller that sums the workspace over the shards in between:
+ * dgg_csr_norm_bwd_acc_rows ACCUMULATES d loss / d rs^-1/2 into da_ws [N] at row0 + i and at col_e (float atomics; entries with
+ * dA_e w_e == 0 add nothing) and writes nothing else -- da_ws must hold zeros, or the shares other slices already added;
+ * dgg_csr_norm_bwd_apply_rows reads da_ws at row0 + i only -- it must then hold the SUM of every slice's share (one rank: after all acc
+ * calls; several ranks: after an all-reduce) -- and overwrites dw [E_loc] on every entry. */
+int dgg_csr_normalize_fwd_rows(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, int64_t row0, int64_t n,
+                               int64_t N, float *ahat, void *stream);
+int dgg_csr_norm_bwd_acc_rows(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, const float *dA, int64_t row0,
+                              int64_t n, int64_t N, float *da_ws, void *stream);
+int dgg_csr_norm_bwd_apply_rows(const int64_t *rowptr, const int32_t *col, const float *rs, const float *dA, const float *da_ws,
+                                int64_t row0, int64_t n, int64_t N, float *dw, void *stream);
 /* torch.mm(adj, x) (model.py:594) on the CSR pattern: Y [N,F] overwritten on every row (an empty row: zeros); N == 0 or F == 0
  * returns 0.  Its autograd: dA [E] overwritten, the same bits with dX == NULL; dX [N,F] (nullable) is ACCUMULATED into (float atomics
  * on row col_e of every entry with a_e != 0): it must hold the caller's start value (zeros for the plain gradient); rows of nodes

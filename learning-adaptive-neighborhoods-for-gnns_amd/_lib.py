@@ -68,6 +68,7 @@ PROTOTYPES = {
     "dgg_edge_mlp_bwd_partp_rows": [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "dgg_csr_softk_fwd": [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _u32, _u32, _i32, _vp, _vp, _vp, _vp],
     "dgg_csr_softk_bwd": [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "dgg_csr_softk_fwd_rows": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _u32, _u32, _i32, _vp, _vp, _vp, _vp],
     "dgg_csr_rank_ramp_fwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dgg_csr_rank_ramp_bwd": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dgg_csr_noisy_sigmoid_fwd": [_vp, _vp, _i64, _vp, _vp],
@@ -81,11 +82,16 @@ PROTOTYPES = {
     "dgg_feat_softmax_bwd": [_vp, _vp, _i64, _i32, _vp, _vp],
     "dgg_csr_uvdist_fwd": [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp],
     "dgg_csr_uvdist_bwd": [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp],
+    "dgg_csr_uvdist_fwd_rows": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _vp, _vp],
+    "dgg_csr_uvdist_bwd_rows": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _vp],
     "dgg_csr_perturb_fwd": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _u32, _u32, _vp, _vp],
     "dgg_csr_perturb_bwd": [_vp, _vp, _vp, _i64, _vp, _vp],
     "dgg_csr_row_sum": [_vp, _vp, _i64, _vp, _vp],
     "dgg_csr_normalize_fwd": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "dgg_csr_norm_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "dgg_csr_normalize_fwd_rows": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
+    "dgg_csr_norm_bwd_acc_rows": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
+    "dgg_csr_norm_bwd_apply_rows": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
     "dgg_csr_spmm_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
     "dgg_csr_bg_softmax_fwd": [_vp, _vp, _i64, _vp, _vp, _vp],
     "dgg_csr_bg_softmax_bwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],

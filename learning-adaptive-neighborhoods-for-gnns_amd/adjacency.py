@@ -114,11 +114,14 @@ class EllAdjacency:
 
 class CsrAdjacency:
     """Sparse matrix with the pattern of a coalesced COO in_adj (rowptr int64 [N+1], col int32 [E], erow int32 [E]) and
-    its own values [E]: what the `DGG` class returns (every candidate edge kept, dgm.py:1804-1815), rows of any width."""
+    its own values [E]: what the `DGG` class returns (every candidate edge kept, dgm.py:1804-1815), rows of any width.
+    row0 / n_rows: the rows [row0, row0 + n_rows) of such a matrix as a row shard holds them (csr_pattern_rows): shape (n_rows, n),
+    rowptr [n_rows + 1] from 0, col and erow GLOBAL; to_dense() / to_sparse() place row erow - row0."""
 
-    def __init__(self, rowptr, col, erow, values, n, k=None):
+    def __init__(self, rowptr, col, erow, values, n, k=None, row0=0, n_rows=None):
         self.rowptr, self.col, self.erow, self._values, self.k = rowptr, col, erow, values, k
-        self.shape = (n, n)
+        self.row0 = int(row0)
+        self.shape = (n if n_rows is None else int(n_rows), n)
         self.device = values.device
 
     def values(self):
@@ -128,16 +131,18 @@ class CsrAdjacency:
         return self
 
     def indices(self):
-        return torch.stack([self.erow.long(), self.col.long()])
+        return torch.stack([self.erow.long() - self.row0, self.col.long()])
 
     def to_sparse(self):
         return torch.sparse_coo_tensor(self.indices(), self._values, self.shape)
 
     def to_dense(self):
         out = torch.zeros(self.shape, device=self.device, dtype=self._values.dtype)
-        return out.index_put((self.erow.long(), self.col.long()), self._values, accumulate=True)
+        return out.index_put((self.erow.long() - self.row0, self.col.long()), self._values, accumulate=True)
 
     def normalize(self):
+        if self.shape[0] != self.shape[1]:
+            raise NotImplementedError("CsrAdjacency.normalize: a row shard needs the other shards' row sums (dgg_amd.distributed)")
         return CsrAdjacency(self.rowptr, self.col, self.erow, ops.CsrNormalizeFn.apply(self._values, self.rowptr, self.col),
                             self.shape[0], k=self.k)
 
@@ -177,6 +182,19 @@ def csr_pattern(in_adj):
         rowptr = torch._convert_indices_from_coo_to_csr(ind[0], a.shape[0], out_int32=False)
         return rowptr, ind[1].to(torch.int32).contiguous(), ind[0].to(torch.int32).contiguous()
     return _cached("pattern", in_adj, make)
+
+
+def csr_pattern_rows(in_adj, rows):
+    """rows [r0, r1) of csr_pattern(in_adj) as a row shard takes them -> ((rowptr int64 [r1-r0+1] REBASED to start at 0, col int32
+    [E_loc] global, erow int32 [E_loc] global), (e0, e1)): per-edge arrays of the whole graph are sliced to [e0, e1).  Cached with the
+    graph (one host read of two offsets per graph object and row range)."""
+    r0, r1 = int(rows[0]), int(rows[1])
+
+    def make():
+        rowptr, col, erow = csr_pattern(in_adj)
+        e0, e1 = (int(v) for v in rowptr[[r0, r1]].tolist())
+        return ((rowptr[r0:r1 + 1] - e0).contiguous(), col[e0:e1], erow[e0:e1]), (e0, e1)
+    return _cached(("pattern_rows", r0, r1), in_adj, make)
 
 
 def ell_from_dense(A, K=ops.DEFAULT_K):

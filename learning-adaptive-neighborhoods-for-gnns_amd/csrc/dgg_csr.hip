@@ -35,11 +35,11 @@ __global__ __launch_bounds__(WPB * 64) void csr_row_sum_kernel(const float *__re
 
 __global__ __launch_bounds__(WPB * 64) void csr_normalize_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                 const float *__restrict__ w, const float *__restrict__ rs,
-                                                                int64_t N, float *__restrict__ ahat) {
+                                                                int64_t N, int64_t row0, float *__restrict__ ahat) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
     if (i >= N) return;
-    const float ai = __fdiv_rn(1.0f, c_sqrt(rs[i]));
+    const float ai = __fdiv_rn(1.0f, c_sqrt(rs[row0 + i]));
     for (int64_t e = rowptr[i] + lane; e < rowptr[i + 1]; e += 64)
         ahat[e] = __fmul_rn(__fmul_rn(ai, w[e]), __fdiv_rn(1.0f, c_sqrt(rs[col[e]])));
 }
@@ -93,11 +93,12 @@ __global__ __launch_bounds__(WPB * 64) void csr_spmm_bwd_kernel(const int64_t *_
 // normalisation backward, phase 1: da_i += sum_e g_e a_j (row, plain add by one lane), da_j += g_e a_i (atomics); g = dA w
 __global__ __launch_bounds__(WPB * 64) void csr_norm_bwd_da_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                   const float *__restrict__ w, const float *__restrict__ rs,
-                                                                  const float *__restrict__ dA, int64_t N, float *__restrict__ da) {
+                                                                  const float *__restrict__ dA, int64_t N, int64_t row0,
+                                                                  float *__restrict__ da) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
     if (i >= N) return;
-    const float ai = 1.0f / sqrtf(rs[i]);
+    const float ai = 1.0f / sqrtf(rs[row0 + i]);
     float rowpart = 0.0f;
     for (int64_t e = rowptr[i] + lane; e < rowptr[i + 1]; e += 64) {
         const float g = dA[e] * w[e];
@@ -108,17 +109,18 @@ __global__ __launch_bounds__(WPB * 64) void csr_norm_bwd_da_kernel(const int64_t
         }
     }
     rowpart = wave_sum_dpp(rowpart, lane);
-    if (lane == 0 && rowpart != 0.0f) atomicAdd(da + i, rowpart);
+    if (lane == 0 && rowpart != 0.0f) atomicAdd(da + row0 + i, rowpart);
 }
 // phase 2: dw_e = dA_e a_i a_j + drs_i, drs_i = -0.5 da_i a_i / rs_i
 __global__ __launch_bounds__(WPB * 64) void csr_norm_bwd_dw_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                   const float *__restrict__ rs, const float *__restrict__ dA,
-                                                                  const float *__restrict__ da, int64_t N, float *__restrict__ dw) {
+                                                                  const float *__restrict__ da, int64_t N, int64_t row0,
+                                                                  float *__restrict__ dw) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
     if (i >= N) return;
-    const float ai = 1.0f / sqrtf(rs[i]);
-    const float drs = -0.5f * da[i] * ai / rs[i];
+    const float ai = 1.0f / sqrtf(rs[row0 + i]);
+    const float drs = -0.5f * da[row0 + i] * ai / rs[row0 + i];
     for (int64_t e = rowptr[i] + lane; e < rowptr[i + 1]; e += 64) dw[e] = dA[e] * ai * (1.0f / sqrtf(rs[col[e]])) + drs;
 }
 
@@ -191,8 +193,8 @@ __global__ __launch_bounds__(WPB * 64) void csr_rank_ramp_bwd_kernel(const float
 // in_adj: perturbation (dgm.py:1213-1229), position of every candidate in its row's sort (counting; ties: lower column first),
 // ramp 1 - 0.5 (1 + tanh(pos - k_i)), w = p' * ramp (k_times_edge_prob) or ramp (k_only).  One wavefront per row.
 __global__ __launch_bounds__(WPB * 64) void csr_softk_fwd_kernel(const float *__restrict__ p, const int64_t *__restrict__ rowptr,
-                                                                const int32_t *__restrict__ col, int64_t N, const float *__restrict__ k,
-                                                                int noise_mode, const float *__restrict__ G, int64_t ldG, uint32_t s0,
+                                                                const int32_t *__restrict__ col, int64_t N, int64_t row0,
+                                                                const float *__restrict__ k, int noise_mode, const float *__restrict__ G, int64_t ldG, uint32_t s0,
                                                                 uint32_t s1, int mode, float *__restrict__ w, float *__restrict__ pp,
                                                                 int32_t *__restrict__ pos) {
     const int lane = threadIdx.x & 63;
@@ -200,11 +202,12 @@ __global__ __launch_bounds__(WPB * 64) void csr_softk_fwd_kernel(const float *__
     if (i >= N) return;
     const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
     const float ki = k[i];
+    const int64_t u = row0 + i;                                  // (i: the slice's row, u: its node -- the noise is keyed on the global pair)
     auto perturbed = [&](int64_t e) {
         const float pe = p[e];
         if (noise_mode == 0) return pe;
         const int32_t j = col[e];
-        const float g = noise_mode == 1 ? G[i * ldG + j] : pair_noise(s0, s1, (uint32_t)i, (uint32_t)j, noise_mode == 3);
+        const float g = noise_mode == 1 ? G[u * ldG + j] : pair_noise(s0, s1, (uint32_t)u, (uint32_t)j, noise_mode == 3);
         return c_exp(__fadd_rn(c_log(__fadd_rn(pe, 1e-8f)), g));
     };
     for (int64_t e = e0 + lane; e < e1; e += 64) pp[e] = perturbed(e);
@@ -300,12 +303,12 @@ __global__ __launch_bounds__(256) void csr_rank_cut_bwd_kernel(const int32_t *__
 // probabilities back (src = s_edge_p), so its output is edge_p as well.  u-v-dist scorer on the stored entries of in_adj
 // (dgm.py:1613-1627): p_e = exp(t ||xp_u - xp_v||), lane = entry, canonical distance.
 __global__ __launch_bounds__(WPB * 64) void csr_uvdist_fwd_kernel(const float *__restrict__ xp, const int64_t *__restrict__ rowptr,
-                                                                 const int32_t *__restrict__ col, int64_t N, int h, float t,
-                                                                 float *__restrict__ p) {
+                                                                 const int32_t *__restrict__ col, int64_t N, int64_t row0, int h,
+                                                                 float t, float *__restrict__ p) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
     if (i >= N) return;
-    const float *xi = xp + i * h;
+    const float *xi = xp + (row0 + i) * h;
     for (int64_t e = rowptr[i] + lane; e < rowptr[i + 1]; e += 64) {
         const float d = c_sqrt(pair_d2_thread(xi, xp + (int64_t)col[e] * h, h));
         p[e] = c_exp(__fmul_rn(t, d));
@@ -314,13 +317,14 @@ __global__ __launch_bounds__(WPB * 64) void csr_uvdist_fwd_kernel(const float *_
 // dp -> dxp (accumulated onto the caller's start value): lane = feature, entries of the row in sequence; own row by plain accumulation in
 // registers, neighbour rows by float atomics (edge lists are small: the 100k-node path never comes here)
 __global__ __launch_bounds__(WPB * 64) void csr_uvdist_bwd_kernel(const float *__restrict__ xp, const int64_t *__restrict__ rowptr,
-                                                                 const int32_t *__restrict__ col, int64_t N, int h, float t,
-                                                                 const float *__restrict__ p, const float *__restrict__ dp,
+                                                                 const int32_t *__restrict__ col, int64_t N, int64_t row0, int h,
+                                                                 float t, const float *__restrict__ p, const float *__restrict__ dp,
                                                                  float *__restrict__ dxp) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
     if (i >= N) return;
-    const float *xi = xp + i * h;
+    const float *xi = xp + (row0 + i) * h;
+    float *dxi = dxp + (row0 + i) * h;
     for (int64_t e = rowptr[i]; e < rowptr[i + 1]; e++) {
         const float g = dp[e] * p[e] * t;                          // d loss / d dist
         if (g == 0.0f) continue;
@@ -334,7 +338,7 @@ __global__ __launch_bounds__(WPB * 64) void csr_uvdist_bwd_kernel(const float *_
         const float coef = g / sqrtf(d2);
         for (int c = lane; c < h; c += 64) {
             const float v = coef * (xi[c] - xj[c]);
-            atomicAdd(dxp + i * h + c, v);
+            atomicAdd(dxi + c, v);
             atomicAdd(dxp + j * h + c, -v);
         }
     }
@@ -435,6 +439,9 @@ __global__ void pair_keep_kernel(const int32_t *__restrict__ erow, const int32_t
 
 }  // namespace
 
+// a row range of a CSR slice: rows [row0, row0 + n) of a pattern over N nodes (columns and node ids are int32 / uint32 hash keys)
+static bool rows_ok(int64_t row0, int64_t n, int64_t N) { return row0 >= 0 && n >= 0 && N >= 0 && N <= 0x7fffffffll && row0 <= N - n; }
+
 extern "C" {
 
 int dgg_csr_bg_softmax_fwd(const float *L, const int64_t *rowptr, int64_t N, float *att, float *bg, void *stream) {
@@ -483,8 +490,17 @@ int dgg_csr_normalize_fwd(const int64_t *rowptr, const int32_t *col, const float
                           void *stream) {
     if (N == 0) return 0;
     hipLaunchKernelGGL(csr_normalize_kernel, dim3((unsigned)((N + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, w,
-                       rs, N, ahat);
+                       rs, N, (int64_t)0, ahat);
     return dgg_check_launch("csr_normalize_fwd");
+}
+// rows [row0, row0 + n) of the pattern as a rebased slice (rowptr [n+1] from 0, global col): rs [N] every node's, ahat [E_loc] overwritten
+int dgg_csr_normalize_fwd_rows(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, int64_t row0, int64_t n,
+                               int64_t N, float *ahat, void *stream) {
+    if (!rows_ok(row0, n, N)) return dgg_set_error(DGG_ERR_ARG, "csr_normalize_fwd_rows: rows must satisfy 0 <= row0 <= row0 + n <= N < 2^31");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(csr_normalize_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, w,
+                       rs, n, row0, ahat);
+    return dgg_check_launch("csr_normalize_fwd_rows");
 }
 
 int dgg_csr_spmm_fwd(const int64_t *rowptr, const int32_t *col, const float *a, const float *X, int64_t N, int F, float *Y,
@@ -509,9 +525,28 @@ int dgg_csr_norm_bwd(const int64_t *rowptr, const int32_t *col, const float *w, 
                      float *da_ws, float *dw, void *stream) {
     if (N == 0) return 0;
     const dim3 grid((unsigned)((N + WPB - 1) / WPB));
-    hipLaunchKernelGGL(csr_norm_bwd_da_kernel, grid, dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, w, rs, dA, N, da_ws);
-    hipLaunchKernelGGL(csr_norm_bwd_dw_kernel, grid, dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, rs, dA, da_ws, N, dw);
+    hipLaunchKernelGGL(csr_norm_bwd_da_kernel, grid, dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, w, rs, dA, N, (int64_t)0, da_ws);
+    hipLaunchKernelGGL(csr_norm_bwd_dw_kernel, grid, dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, rs, dA, da_ws, N, (int64_t)0, dw);
     return dgg_check_launch("csr_norm_bwd");
+}
+// the two halves of dgg_csr_norm_bwd on rows [row0, row0 + n) of the pattern, for a caller that sums da_ws over row shards in between.
+// acc: da_ws [N] accumulated into at row0 + i and at col_e (the caller's start value: zeros); nothing else written
+int dgg_csr_norm_bwd_acc_rows(const int64_t *rowptr, const int32_t *col, const float *w, const float *rs, const float *dA, int64_t row0,
+                              int64_t n, int64_t N, float *da_ws, void *stream) {
+    if (!rows_ok(row0, n, N)) return dgg_set_error(DGG_ERR_ARG, "csr_norm_bwd_acc_rows: rows must satisfy 0 <= row0 <= row0 + n <= N < 2^31");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(csr_norm_bwd_da_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, w, rs,
+                       dA, n, row0, da_ws);
+    return dgg_check_launch("csr_norm_bwd_acc_rows");
+}
+// apply: da_ws [N] the sum of every slice's acc (read at row0 + i only) -> dw [E_loc] overwritten
+int dgg_csr_norm_bwd_apply_rows(const int64_t *rowptr, const int32_t *col, const float *rs, const float *dA, const float *da_ws,
+                                int64_t row0, int64_t n, int64_t N, float *dw, void *stream) {
+    if (!rows_ok(row0, n, N)) return dgg_set_error(DGG_ERR_ARG, "csr_norm_bwd_apply_rows: rows must satisfy 0 <= row0 <= row0 + n <= N < 2^31");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(csr_norm_bwd_dw_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, rowptr, col, rs,
+                       dA, da_ws, n, row0, dw);
+    return dgg_check_launch("csr_norm_bwd_apply_rows");
 }
 
 // select_top_k on the CSR pattern (rows of any width; dgm.py:1402-1435): p [E] edge probabilities, k [N] learned degrees;
@@ -522,9 +557,22 @@ int dgg_csr_softk_fwd(const float *p, const int64_t *rowptr, const int32_t *col,
     if (noise_mode < 0 || noise_mode > 3 || (noise_mode == 1 && !G)) return dgg_set_error(DGG_ERR_ARG, "csr_softk_fwd: bad noise arguments");
     if (mode != 0 && mode != 1) return dgg_set_error(DGG_ERR_ARG, "csr_softk_fwd: mode must be 0 (k_times_edge_prob) or 1 (k_only)");
     if (N == 0) return 0;
-    hipLaunchKernelGGL(csr_softk_fwd_kernel, dim3((unsigned)((N + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, p, rowptr, col, N, k,
-                       noise_mode, G, ldG, s0, s1, mode, w, pp, pos);
+    hipLaunchKernelGGL(csr_softk_fwd_kernel, dim3((unsigned)((N + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, p, rowptr, col, N,
+                       (int64_t)0, k, noise_mode, G, ldG, s0, s1, mode, w, pp, pos);
     return dgg_check_launch("csr_softk_fwd");
+}
+// rows [row0, row0 + n) of the pattern as a rebased slice: k [n] the slice's learned degrees, the hash noise keyed on the GLOBAL pair
+// (row0 + i, col) -- the realisation does not depend on how the rows are split; noise_mode 0 none / 2 hash / 3 symmetric hash
+int dgg_csr_softk_fwd_rows(const float *p, const int64_t *rowptr, const int32_t *col, int64_t row0, int64_t n, int64_t N, const float *k,
+                           int noise_mode, uint32_t s0, uint32_t s1, int mode, float *w, float *pp, int32_t *pos, void *stream) {
+    if (noise_mode != 0 && noise_mode != 2 && noise_mode != 3)
+        return dgg_set_error(DGG_ERR_ARG, "csr_softk_fwd_rows: noise_mode 0 (none), 2 (hash) or 3 (symmetric hash); explicit noise is not sliced");
+    if (mode != 0 && mode != 1) return dgg_set_error(DGG_ERR_ARG, "csr_softk_fwd_rows: mode must be 0 (k_times_edge_prob) or 1 (k_only)");
+    if (!rows_ok(row0, n, N)) return dgg_set_error(DGG_ERR_ARG, "csr_softk_fwd_rows: rows must satisfy 0 <= row0 <= row0 + n <= N < 2^31");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(csr_softk_fwd_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, p, rowptr, col, n,
+                       row0, k, noise_mode, (const float *)nullptr, (int64_t)0, s0, s1, mode, w, pp, pos);
+    return dgg_check_launch("csr_softk_fwd_rows");
 }
 int dgg_csr_softk_bwd(const float *p, const float *pp, const int64_t *rowptr, int64_t N, const float *k, const int32_t *pos, int perturb,
                       int mode, const float *g, float *dp, float *dk, void *stream) {
@@ -602,16 +650,37 @@ int dgg_csr_uvdist_fwd(const float *xp, const int64_t *rowptr, const int32_t *co
     if (N == 0) return 0;
     if (h < 1) return dgg_set_error(DGG_ERR_ARG, "csr_uvdist_fwd: h must be positive");
     hipLaunchKernelGGL(csr_uvdist_fwd_kernel, dim3((unsigned)((N + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, xp, rowptr, col,
-                       N, h, t, p);
+                       N, (int64_t)0, h, t, p);
     return dgg_check_launch("csr_uvdist_fwd");
+}
+// rows [row0, row0 + n) of the pattern as a rebased slice: xp [N,h] every node's (row side read at row0 + i), p [E_loc] overwritten
+int dgg_csr_uvdist_fwd_rows(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t row0, int64_t n, int64_t N, int h, float t,
+                            float *p, void *stream) {
+    if (!rows_ok(row0, n, N)) return dgg_set_error(DGG_ERR_ARG, "csr_uvdist_fwd_rows: rows must satisfy 0 <= row0 <= row0 + n <= N < 2^31");
+    if (h < 1) return dgg_set_error(DGG_ERR_ARG, "csr_uvdist_fwd_rows: h must be positive");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(csr_uvdist_fwd_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, xp, rowptr, col,
+                       n, row0, h, t, p);
+    return dgg_check_launch("csr_uvdist_fwd_rows");
 }
 
 int dgg_csr_uvdist_bwd(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t N, int h, float t, const float *p,
                        const float *dp, float *dxp, void *stream) {
     if (N == 0) return 0;
     hipLaunchKernelGGL(csr_uvdist_bwd_kernel, dim3((unsigned)((N + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, xp, rowptr, col,
-                       N, h, t, p, dp, dxp);
+                       N, (int64_t)0, h, t, p, dp, dxp);
     return dgg_check_launch("csr_uvdist_bwd");
+}
+// the slice's share of the gradient: dxp [N,h] accumulated into at rows row0 + i and col_e (the caller's start value: zeros, or another
+// slice's share)
+int dgg_csr_uvdist_bwd_rows(const float *xp, const int64_t *rowptr, const int32_t *col, int64_t row0, int64_t n, int64_t N, int h, float t,
+                            const float *p, const float *dp, float *dxp, void *stream) {
+    if (!rows_ok(row0, n, N)) return dgg_set_error(DGG_ERR_ARG, "csr_uvdist_bwd_rows: rows must satisfy 0 <= row0 <= row0 + n <= N < 2^31");
+    if (h < 1) return dgg_set_error(DGG_ERR_ARG, "csr_uvdist_bwd_rows: h must be positive");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(csr_uvdist_bwd_kernel, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, xp, rowptr, col,
+                       n, row0, h, t, p, dp, dxp);
+    return dgg_check_launch("csr_uvdist_bwd_rows");
 }
 
 }  // extern "C"

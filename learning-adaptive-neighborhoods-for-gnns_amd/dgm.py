@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .adjacency import AllPairs, CsrAdjacency, EllAdjacency, _cached, csr_candidates, csr_pattern
+from .adjacency import AllPairs, CsrAdjacency, EllAdjacency, _cached, csr_candidates, csr_pattern, csr_pattern_rows
 
 _EDGE_MLP_MODES = ("u-v-A_uv", "u-v-deg", "u-v-deg-dist", "edge_conv", "A_uv")
 
@@ -267,7 +267,9 @@ class _DGGEdgeMlpAdjFn(torch.autograd.Function):
 class _DGGScoresFn(torch.autograd.Function):
     """Raw edge probabilities on the stored entries of in_adj, CSR order (reference edge_prob_net, dgm.py:1607-1725), for the
     forward variants that return them as the adjacency: debug_step 0 / 1 (dgm.py:1202-1209, 1240-1246) and the k-select mode
-    `edge_p-cdf`, which scatters the unsorted probabilities back (dgm.py:1400)."""
+    `edge_p-cdf`, which scatters the unsorted probabilities back (dgm.py:1400).
+    cfg["rows"] = (r0, r1): cfg["cand"] is the slice of a row shard (adjacency.csr_pattern_rows) and ex_in its entries'; x and deg stay
+    the whole graph's, and the backward returns the shard's SHARE of every gradient (the caller sums the shards')."""
 
     @staticmethod
     def forward(ctx, x, deg, ex_in, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
@@ -275,7 +277,7 @@ class _DGGScoresFn(torch.autograd.Function):
         rowptr, col, erow = cfg["cand"]
         ctx.cfg = cfg
         if Wcat is None:                                  # u-v-dist
-            p = ops.csr_uvdist_fwd(xp, rowptr, col, cfg["t"])
+            p = ops.csr_uvdist_fwd(xp, rowptr, col, cfg["t"], rows=cfg.get("rows"))
             ctx.opt = ()
             ctx.save_for_backward(x, We, xp, p)
             return p
@@ -290,20 +292,21 @@ class _DGGScoresFn(torch.autograd.Function):
     def backward(ctx, dp):
         cfg = ctx.cfg
         rowptr, col, _ = cfg["cand"]
+        rows = cfg.get("rows")                            # (a row shard's slice: xp / AB / deg of every node, partial sums out)
         dp = dp.contiguous()
         if not ctx.opt:
             x, We, xp, p = ctx.saved_tensors
-            dxp = ops.csr_uvdist_bwd(xp, rowptr, col, p, dp, cfg["t"])
+            dxp = ops.csr_uvdist_bwd(xp, rowptr, col, p, dp, cfg["t"], rows=rows)
             dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
             return (dx, None, None, dWe, dbe) + (None,) * 8
         x, We, xp, p, AB, Wcat, eb1, w2, b2 = ctx.saved_tensors
         sdeg, ex, wdu, wdv, wex = ctx.opt
         hw = Wcat.shape[0] // 2
         dAB, dpar, dex = ops.edge_mlp_bwd(AB, col, None, p, dp, sdeg, ex, wdu, wdv, wex, eb1, w2, b2, cfg["act"], False,
-                                          need_dex=cfg["ex_mode"] == 2, rowptr=rowptr)
+                                          need_dex=cfg["ex_mode"] == 2, rowptr=rowptr, rows=rows)
         dxp, dWcat, _ = ops.linear_bwd(xp, Wcat, AB, dAB, ops.ACT_NONE, need_dx=True, need_db=False)
         if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
-            dxp = dxp + ops.csr_uvdist_bwd(xp, rowptr, col, ex, dex, cfg["t_ex"])
+            dxp = dxp + ops.csr_uvdist_bwd(xp, rowptr, col, ex, dex, cfg["t_ex"], rows=rows)
         dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
         g = lambda t_, a, b: None if t_ is None else dpar[a:b]  # noqa: E731
         return (dx, None, None, dWe, dbe, dWcat if ctx.needs_input_grad[5] else None, g(wdu, 0, hw), g(wdv, hw, 2 * hw),
@@ -976,22 +979,32 @@ class DGG_LearnableK_debug(nn.Module):
             st["on"] = bool((k.detach() + 8.5 > float(self.ell_width)).any().item())
         return st["on"]
 
-    def _csr_soft_adjacency(self, x, in_adj, k, noise_mode, G, seed, mode, pattern=None, deg=None):
+    def _csr_soft_adjacency(self, x, in_adj, k, noise_mode, G, seed, mode, pattern=None, deg=None, rows=None):
         """select_top_k on the CSR pattern of in_adj (ops.CsrSoftkFn: rows of any width, exact for any learned degree): edge
         probabilities as in _scores_adjacency, then perturbation + rank + ramp per row.  pattern / deg given (all-pairs candidates):
-        the complete pattern, no in_adj."""
+        the complete pattern, no in_adj.
+        rows = (r0, r1) (dgg_amd.distributed.ShardedGCN_DGG): rows [r0, r1) of in_adj only, k their learned degrees [r1 - r0]; x and the
+        projection stay the whole graph's -> the CsrAdjacency of those rows (global columns, the bits of the whole graph's rows), whose
+        backward leaves the shard's share of every gradient."""
         if pattern is None:
             in_adj = in_adj.coalesce()
             pattern = csr_pattern(in_adj)
             _, _, deg = csr_candidates(in_adj)
+        if rows is not None:
+            assert in_adj is not None and G is None and not self.hard, "a row shard: edge-list candidates, counter-based noise, soft output"
+            pattern, (e0, e1) = csr_pattern_rows(in_adj, rows)
         We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
-        cfg = dict(cand=pattern, t=ops.T_DIST)
+        cfg = dict(cand=pattern, t=ops.T_DIST, rows=rows)
         if self.edge_prob_net_mode == "u-v-dist":
             p = _DGGScoresFn.apply(x, None, None, We, be, None, None, None, None, None, None, None, cfg)
         else:
-            mlp, ex_in = self._edge_mlp_terms(in_adj.values().to(torch.float32))
+            avals = in_adj.values().to(torch.float32)
+            mlp, ex_in = self._edge_mlp_terms(avals if rows is None else avals[e0:e1])
             cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
             p = _DGGScoresFn.apply(x, deg, ex_in, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"], mlp["w2"], mlp["b2"], cfg)
+        if rows is not None:
+            w = ops.CsrSoftkRowsFn.apply(p, k, pattern[0], pattern[1], rows, x.shape[0], noise_mode, seed, mode)
+            return CsrAdjacency(pattern[0], pattern[1], pattern[2], w, x.shape[0], k=k.detach(), row0=rows[0], n_rows=rows[1] - rows[0])
         w = ops.CsrSoftkFn.apply(p, k, pattern[0], pattern[1], noise_mode, G, seed, mode)
         if self.hard and mode == ops.MODE_K_TIMES_EDGE_PROB:      # straight-through (see forward): ramp mask forward, soft gradient
             ramp = ops.CsrSoftkFn.apply(p.detach(), k.detach(), pattern[0], pattern[1], noise_mode, G, seed, ops.MODE_K_ONLY)
@@ -1050,6 +1063,22 @@ class DGG_LearnableK_debug(nn.Module):
                      b2=torch.zeros_like(self.adj_project.bias), wex=w.reshape(-1), ex_mode=1, act=ops.ACT_NONE)
             ex_in = avals
         return d, ex_in
+
+    def _project_for_k(self, x, literal=False):
+        """k-net modes x / gcn-x-deg: leaky(x Wk + bk), together with the scorer's projection where one pass over x serves both
+        -> (xp or None, xk)"""
+        We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
+        Wk, bk = self.node_encode_for_k[0].weight, self.node_encode_for_k[0].bias
+        if (self.edge_prob_net_mode == "u-v-dist" and not literal and We.shape[0] % 32 == 0 and Wk.shape[0] % 32 == 0
+                and We.shape[0] + Wk.shape[0] <= 256 and getattr(self.args, "dgg_fused_projections", True)):
+            return _DualProjFn.apply(x, We, be, Wk, bk)           # both projections on one pass over x
+        return None, ops.LinearFn.apply(x, Wk, bk, ops.ACT_LEAKY, 0)
+
+    def _knet_feat(self, xk, deg):
+        """the k-net on projected features and ALL nodes' prior degrees (their mean and std normalise them) -> k [N]"""
+        kn = self.k_net
+        return _KnetFeatFn.apply(xk, deg, self.k_embed[0].weight, self.k_embed[0].bias, kn.k_mu.weight, kn.k_mu.bias,
+                                 kn.k_project.weight, kn.k_project.bias, getattr(self, "gemm_dtype", None) == torch.bfloat16)
 
     @staticmethod
     def _norm_deg(deg, consts, eps):
@@ -1157,12 +1186,7 @@ class DGG_LearnableK_debug(nn.Module):
         kn = self.k_net
         xp_dual = None
         if self.k_net_mode in ("x", "gcn-x-deg"):
-            Wk, bk = self.node_encode_for_k[0].weight, self.node_encode_for_k[0].bias
-            if (self.edge_prob_net_mode == "u-v-dist" and not literal and We.shape[0] % 32 == 0 and Wk.shape[0] % 32 == 0
-                    and We.shape[0] + Wk.shape[0] <= 256 and getattr(self.args, "dgg_fused_projections", True)):
-                xp_dual, xk = _DualProjFn.apply(x, We, be, Wk, bk)       # both projections on one pass over x
-            else:
-                xk = ops.LinearFn.apply(x, Wk, bk, ops.ACT_LEAKY, 0)
+            xp_dual, xk = self._project_for_k(x, literal)
             if self.k_net_mode == "gcn-x-deg":       # relu(normalize_adj(in_adj) @ xk @ k_W)   (dgm.py:1528-1540)
                 if cand is None:
                     raise NotImplementedError("k-net mode 'gcn-x-deg' aggregates over the stored entries of in_adj")
@@ -1172,8 +1196,7 @@ class DGG_LearnableK_debug(nn.Module):
             if getattr(self.args, "stochastic_k", False) and self.training:
                 k = self._stochastic_k(torch.cat([xk, self._norm_deg(deg, None, 1e-5)[0].unsqueeze(1)], 1), deg, None, embed=True)
             else:
-                k = _KnetFeatFn.apply(xk, deg, self.k_embed[0].weight, self.k_embed[0].bias, kn.k_mu.weight, kn.k_mu.bias,
-                                      kn.k_project.weight, kn.k_project.bias, getattr(self, "gemm_dtype", None) == torch.bfloat16)
+                k = self._knet_feat(xk, deg)
         elif getattr(self.args, "stochastic_k", False) and self.training:
             consts = (float(self.deg_mean), float(self.deg_std)) if self.k_net_mode == "input_deg" else None
             nd, _, _ = self._norm_deg(deg, consts, 1e-5 if consts is not None else 0.0)

@@ -13,10 +13,19 @@ over the ranks inside their autograd nodes, so identical optimisers keep the ran
 
 Edge-list candidates (a sparse in_adj, the reference's own configuration: dgm.py:1613-1614) run on several ranks with the u-v-dist scorer
 and the edge-MLP scorers of the fused layer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv, A_uv), under no / hash / symmetric hash noise:
-every rank scores its own rows' candidates through the row-range kernels, and the scorer's gradients are summed with the layer's.  Rows
-wider than the 64-rank list whose learned degree needs more ranks than that (the one-GPU model's CSR form) are not sharded: that forward
-raises NotImplementedError on every rank at once (the flag is ORed over the ranks).  How the step scales with the number of GPUs has not
-been measured.
+every rank scores its own rows' candidates through the row-range kernels, and the scorer's gradients are summed with the layer's.
+
+Rows wider than the 64-rank list whose learned degree needs more ranks than that leave the fused layer for the CSR form
+(DGG_LearnableK_debug._csr_soft_adjacency -> CsrAdjacency.normalize -> GCNConv on a CsrAdjacency), on one GPU and, as an OPT-IN, on a row
+shard: args.dgg_wide_rows = "csr" (the CSR form from the first forward) or "csr_auto" (the fused layer until the collective wide-row flag
+first fires, the CSR form for that forward -- recomputed -- and every later one on that graph).  Under the default "auto" such a forward
+still raises NotImplementedError on every rank at once (the flag is ORed over the ranks).  The sharded CSR form (_CsrForm) keeps the
+one-GPU operation order, so its forward has the one-GPU bits: every rank computes the projection, the edge-MLP scorer's per-node products
+and the k-net on the whole graph (the k-net normalises with the mean and std of all N prior degrees), scores its own rows' entries
+through the _rows entries of the dgg_csr_* kernels (noise keyed on the global pair), and the step costs, beside the loss's scalar: two
+all-gathers (row sums [N], hidden rows [N, h]), one reduce-scatter (the hidden rows' cotangent), one all-reduce of the normalisation
+backward's workspace [N] and one all-reduce of all parameter gradients in a flat buffer.  No timing of this path exists, and how any of
+the steps scales with the number of GPUs has not been measured.
 
 The reference has no distributed code; its loss is F.nll_loss(out[idx], labels[idx])
 (train_small_graphs.py:226), which global_nll_loss splits over the ranks.
@@ -27,7 +36,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .adjacency import AllPairs
+from .adjacency import AllPairs, CsrAdjacency, csr_candidates
 from .dgm import _capturing
 from .model import GCN_DGG, _with_self_loops
 from .parallel import ShardedDGGConv, _all_gather_rows, shard_bounds
@@ -102,6 +111,104 @@ class _ShardedConvFn(torch.autograd.Function):
         return dx1, dA, dW, None, None, None, None
 
 
+class _SumGradsFn(torch.autograd.Function):
+    """The replicated parameters as the sharded CSR form reads them: identity forward; the backward runs once every use of every
+    parameter has delivered its share and sums all of them over the ranks in ONE all-reduce of a flat buffer, so every rank leaves
+    backward() with the same bits of the full-graph gradient.  A parameter no use reaches gets no gradient, as on one GPU (which ones is
+    a property of the configuration, the same on every rank)."""
+
+    @staticmethod
+    def forward(ctx, group, *params):
+        ctx.group = group
+        ctx.set_materialize_grads(False)
+        return tuple(p_.view_as(p_) for p_ in params)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        have = [g for g in grads if g is not None]
+        if have:
+            flat = torch.cat([g.reshape(-1) for g in have])
+            dist.all_reduce(flat, group=ctx.group)
+            parts = iter(flat.split([g.numel() for g in have]))
+            grads = tuple(None if g is None else next(parts).view(g.shape) for g in grads)
+        return (None,) + grads
+
+
+class _GatherRowsFn(torch.autograd.Function):
+    """the ranks' rows [r1 - r0, c] -> all N rows on every rank; the cotangent -- every rank's partial [N, c] -- is reduce-scattered"""
+
+    @staticmethod
+    def forward(ctx, t, sh):
+        ctx.sh = sh
+        return _all_gather_rows(t, sh.N, sh.per, sh.group)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _reduce_scatter_rows(g, ctx.sh), None
+
+
+class _ShardedCsrNormalizeFn(torch.autograd.Function):
+    """ops.CsrNormalizeFn on a row shard's slice: the shard's row sums are all-gathered (columns name other ranks' rows); the backward
+    runs dgg_csr_norm_bwd's two kernels with the workspace [N] summed over the ranks in between, which also carries the gather's
+    cotangent."""
+
+    @staticmethod
+    def forward(ctx, w, rowptr, col, sh):
+        rs = _all_gather_rows(ops.csr_row_sum(w, rowptr), sh.N, sh.per, sh.group)
+        ahat = ops.csr_normalize_fwd_rows(rowptr, col, w, rs, (sh.r0, sh.r1))
+        ctx.sh = sh
+        ctx.save_for_backward(w, rowptr, col, rs)
+        return ahat
+
+    @staticmethod
+    def backward(ctx, dA):
+        w, rowptr, col, rs = ctx.saved_tensors
+        sh = ctx.sh
+        dA = dA.contiguous()
+        da = ops.csr_norm_bwd_acc_rows(rowptr, col, w, rs, dA, (sh.r0, sh.r1))
+        dist.all_reduce(da, group=sh.group)
+        return ops.csr_norm_bwd_apply_rows(rowptr, col, rs, dA, da, (sh.r0, sh.r1)), None, None, None
+
+
+class _Shard:
+    """rows [r0, r1) of N on rank `rank` of `group` (the fields _reduce_scatter_rows reads from an engine)"""
+
+    def __init__(self, N, world, rank, group):
+        self.N, self.world, self.rank, self.group = N, world, rank, group
+        self.r0, self.r1, self.per = shard_bounds(N, world, rank)
+
+
+class _CsrForm(nn.Module):
+    """The one-GPU CSR form of GCN_DGG (_csr_soft_adjacency -> normalize -> relu((A x) W1) -> dropout -> relu((A x1) W2)) on a row
+    shard, in that operation order.  A module of its own so that torch.func.functional_call can hand it the parameters behind
+    _SumGradsFn: the code below reads them off `model` like any other forward."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+
+    def forward(self, x, in_adj, sh):
+        m = self.model
+        dgg = m.dggs[0]
+        _, _, deg = csr_candidates(in_adj)
+        noise_mode, _, seed = dgg._noise_cfg()               # (edge-list candidates: every candidate is scored, per-pair hash noise)
+        noise_mode = {ops.NOISE_RANKED: ops.NOISE_HASH, ops.NOISE_RANKED_SYM: ops.NOISE_HASH_SYM}.get(noise_mode, noise_mode)
+        mode = ops.MODE_K_TIMES_EDGE_PROB if dgg.k_select_mode == "k_times_edge_prob" else ops.MODE_K_ONLY
+        # replicated: the k-net on the whole graph (its degree normalisation reads all N prior degrees); the shard keeps its rows' k
+        k = dgg._knet_feat(dgg._project_for_k(x)[1], deg)
+        unnorm = dgg._csr_soft_adjacency(x, in_adj, k[sh.r0:sh.r1], noise_mode, None, seed, mode, rows=(sh.r0, sh.r1))
+        rowptr, col = unnorm.rowptr, unnorm.col
+        ahat = _ShardedCsrNormalizeFn.apply(unnorm.values(), rowptr, col, sh)
+        z = ops.LinearFn.apply(ops.CsrSpmmFn.apply(ahat, rowptr, col, x), m.conv1.W, None, ops.ACT_RELU, 1)
+        z = _GatherRowsFn.apply(F.dropout(z, training=m.training), sh)
+        out = ops.LinearFn.apply(ops.CsrSpmmFn.apply(ahat, rowptr, col, z), m.conv2.W, None, ops.ACT_RELU, 1)
+        adj = CsrAdjacency(rowptr, col, unnorm.erow, unnorm.values().detach(), sh.N, k=unnorm.k, row0=sh.r0, n_rows=sh.r1 - sh.r0)
+        return F.log_softmax(out, dim=-1), adj, None
+
+
+_SHARDED_CSR_POLICIES = ("csr", "csr_auto")
+
+
 class ShardedGCN_DGG(nn.Module):
     """GCN_DGG (reference model.py:1183-1311) on a row shard of the graph: rank r of `group` computes rows [r0, r1) = `.rows`
     (parallel.shard_bounds) of the log-probabilities against all N columns.
@@ -114,11 +221,17 @@ class ShardedGCN_DGG(nn.Module):
     EllAdjacency of those rows with global column indices, None).  After backward() every rank holds the full-graph gradient of every
     parameter when the loss is global_nll_loss (or any loss whose per-rank parts sum to the whole).
 
+    Edge-list candidates on several ranks with args.dgg_wide_rows = "csr" / "csr_auto" (opt-in): the sharded CSR form for rows wider than
+    the 64-rank list whose learned degrees outgrow it -- from the first forward ("csr"), or from the forward in which the collective
+    wide-row flag first fires ("csr_auto": that forward is recomputed in CSR form, and the switch is sticky per graph object; all ranks
+    switch in the same forward).  The adjacency returned is then the DETACHED unnormalised CsrAdjacency of the rank's rows
+    (shape (rows, N), global columns); coverage and refusals are those of the fused layer on edge lists (_fused_outside).
+
     Every rank must draw the same noise: seed the CPU generator identically on every rank (torch.manual_seed) or call
     model.dggs[0].set_seed.  The dropout between the layers draws each rank's mask from its own CUDA generator.
     Outside its coverage the wrapper raises (no silent fall-back), before any collective: on several ranks, edge-list candidates whose
-    rows need the CSR form (raised by every rank in the same forward), a writer, configurations the fused layer declines, a hipGraph capture on several ranks, args.dgg_hard_literal,
-    args.dgg_differentiable_adj, args.dgg_wide_rows other than 'auto' / 'chunked', and on several ranks args.dgg_sym_generator = 'auto'
+    rows need the CSR form under the default args.dgg_wide_rows = 'auto' (raised by every rank in the same forward), a writer, configurations the fused layer declines, a hipGraph capture on several ranks, args.dgg_hard_literal,
+    args.dgg_differentiable_adj, args.dgg_wide_rows other than 'auto' / 'chunked' (edge lists on several ranks: or 'csr' / 'csr_auto'), and on several ranks args.dgg_sym_generator = 'auto'
     (a generator switch decided from one rank's rows)."""
 
     def __init__(self, model, group=None):
@@ -183,9 +296,9 @@ class ShardedGCN_DGG(nn.Module):
                 raise NotImplementedError(f"{what}: in_adj must be AllPairs(prior_degree) or the whole graph's [N, N] adjacency "
                                           f"(N = {x.shape[0]}, got {type(in_adj).__name__} {tuple(getattr(in_adj, 'shape', ()))})")
             policy = getattr(a, "dgg_wide_rows", "auto")
-            if policy not in ("auto", "chunked"):
-                raise NotImplementedError(f"{what}: args.dgg_wide_rows = {policy!r} (a row shard keeps the 64-rank list; the CSR form of "
-                                          "rows wider than it is not sharded)")
+            if policy not in ("auto", "chunked") + _SHARDED_CSR_POLICIES:
+                raise NotImplementedError(f"{what}: args.dgg_wide_rows = {policy!r} (a row shard keeps the 64-rank list, or takes the CSR "
+                                          "form of rows wider than it under 'csr' / 'csr_auto')")
             why = dgg._fused_outside(x, in_adj, m.conv1.W)
             if why is not None:
                 raise NotImplementedError(f"{what}: the fused layer does not cover this configuration ({why})")
@@ -213,17 +326,23 @@ class ShardedGCN_DGG(nn.Module):
         edge_lists = self._edge_lists(in_adj)
         if not isinstance(in_adj, AllPairs) and not edge_lists:     # (one rank: edge-list candidates are the model's own step)
             return m(x, in_adj, noise=noise, epoch=epoch, writer=writer)
+        policy = getattr(m.dggs[0].args, "dgg_wide_rows", "auto")
         if edge_lists:
             in_adj = _with_self_loops(in_adj)                # (as GCN_DGG.forward: cached per graph object)
+            if policy == "csr":
+                return self._csr_form(x, in_adj)
         eng = self._engine
         if eng is None or eng.N != N:
             eng = self._engine = ShardedDGGConv(ops, N, group=self.group, K=64, t=ops.T_DIST, x_full=x, hybrid=True)
         got = m.dggs[0]._forward_conv(x, in_adj, m.conv1.W, True, engine=eng)
+        if got is None and edge_lists and policy == "csr_auto" and m.dggs[0]._wide_rows_state(in_adj, csr_candidates(in_adj)[0]) is True:
+            # (decided collectively and sticky per graph: every rank is here in the same forward, and in every later one before any kernel)
+            return self._csr_form(x, in_adj)
         if got is None and edge_lists:
             # (decided collectively: _wide_rows ORs the ranks' flags, so every rank raises here in the same forward)
             raise NotImplementedError("ShardedGCN_DGG (edge-list candidates on several ranks): a row wider than the 64-rank list has a "
-                                      "learned degree beyond it; the CSR form of such rows is not sharded "
-                                      f"({m.dggs[0].__dict__.get('fused_fallback', {})})")
+                                      "learned degree beyond it; the CSR form of such rows is not sharded under args.dgg_wide_rows = "
+                                      f"{policy!r} (opt in with 'csr' or 'csr_auto') ({m.dggs[0].__dict__.get('fused_fallback', {})})")
         if got is None:
             raise NotImplementedError("ShardedGCN_DGG: this forward left the fused layer's coverage "
                                       f"({m.dggs[0].__dict__.get('fused_fallback', {})})")
@@ -231,6 +350,21 @@ class ShardedGCN_DGG(nn.Module):
         z = F.dropout(z, training=m.training)
         out = _ShardedConvFn.apply(z, norm.values(), m.conv2.W, eng, norm.idx, norm.layout, norm.partp)
         return F.log_softmax(out, dim=-1), unnorm, None
+
+
+    def _csr_form(self, x, in_adj):
+        """this forward in the sharded CSR form (edge-list candidates with self loops, several ranks): every rank enters every
+        collective, whether or not it owns a wide row"""
+        m = self.module
+        sh = _Shard(x.shape[0], self.world, self.rank, self.group)
+        named = [(n_, p_) for n_, p_ in m.named_parameters() if p_.requires_grad]
+        params = {}
+        if named and torch.is_grad_enabled():
+            synced = _SumGradsFn.apply(self.group, *[p_ for _, p_ in named])
+            params = {"model." + n_: s_ for (n_, _), s_ in zip(named, synced)}
+        # (tie_weights=False: GCN_DGG lists each GCNConv under two names -- conv1 and convs[0] are ONE module, so the one name
+        #  named_parameters() yields reaches both, and the tie logic would swap that module's slot twice and restore it wrongly)
+        return torch.func.functional_call(_CsrForm(m), params, (x, in_adj, sh), tie_weights=False)
 
 
 _SEL_CACHE = {}

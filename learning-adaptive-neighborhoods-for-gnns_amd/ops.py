@@ -778,6 +778,36 @@ class CsrSoftkFn(torch.autograd.Function):
         return dp, dk, None, None, None, None, None, None
 
 
+class CsrSoftkRowsFn(torch.autograd.Function):
+    """CsrSoftkFn on a row shard's rebased CSR slice (parallel.csr_rows): (p [E_loc], k [r1-r0]) -> w [E_loc], the hash noise keyed on
+    the global pair (dgg_csr_softk_fwd_rows: the bits of the whole graph's rows [r0, r1)).  The backward is dgg_csr_softk_bwd on the slice
+    (no row index reaches a table there)."""
+
+    @staticmethod
+    def forward(ctx, p, k, rowptr, col, rows, N, noise_mode, seed, mode):
+        p, k = _chk(p), _chk(k)
+        r0, n = _rows_of(rowptr, rows, "CsrSoftkRowsFn")
+        assert k.shape[0] == n, "CsrSoftkRowsFn: k [rows] of the rows asked for"
+        w, pp = torch.empty_like(p), torch.empty_like(p)
+        pos = torch.empty(p.shape, device=p.device, dtype=torch.int32)
+        if p.numel():
+            _lib.check(_lib.lib().dgg_csr_softk_fwd_rows(_ptr(p), _ptr(rowptr), _ptr(col), r0, n, int(N), _ptr(k), noise_mode, seed[0], seed[1],
+                                                         mode, _ptr(w), _ptr(pp), _ptr(pos), _stream()), "csr_softk_fwd_rows")
+        ctx.save_for_backward(p, pp, k, pos, rowptr)
+        ctx.cfg = (noise_mode != NOISE_NONE, mode)
+        return w
+
+    @staticmethod
+    def backward(ctx, g):
+        p, pp, k, pos, rowptr = ctx.saved_tensors
+        perturb, mode = ctx.cfg
+        dp, dk = torch.empty_like(p), torch.zeros_like(k)
+        if p.numel():
+            _lib.check(_lib.lib().dgg_csr_softk_bwd(_ptr(p), _ptr(pp), _ptr(rowptr), rowptr.shape[0] - 1, _ptr(k), _ptr(pos), int(perturb), mode,
+                                                    _ptr(_chk(g.contiguous())), _ptr(dp), _ptr(dk), _stream()), "csr_softk_bwd")
+        return dp, dk, None, None, None, None, None, None, None
+
+
 def csr_rank_ramp_fwd(p, rowptr, col, w, b):
     """dgm.py:1791-1812 -> out [E], S [N], k [N], pos [E] (int32)"""
     p = _chk(p)
@@ -915,18 +945,39 @@ class DenseRowsFn(torch.autograd.Function):
         return dense_pairs_dx(xq, Cm), dt_rows.sum().reshape(t.shape), dk, None, None, None, None, None, None
 
 
-def csr_uvdist_fwd(xp, rowptr, col, t=T_DIST):
-    """dgm.py:1613-1627 on the stored entries: p_e = exp(t ||xp_u - xp_v||) -> [E]"""
+def _rows_of(rowptr, rows, what):
+    """(r0, n) of a row shard's rebased CSR slice (parallel.csr_rows): rowptr [n+1] from 0 for rows [r0, r0 + n)"""
+    r0, n = int(rows[0]), int(rows[1]) - int(rows[0])
+    assert rowptr.shape[0] == n + 1, f"{what}: rowptr [rows+1] of the rows asked for"
+    return r0, n
+
+
+def csr_uvdist_fwd(xp, rowptr, col, t=T_DIST, rows=None):
+    """dgm.py:1613-1627 on the stored entries: p_e = exp(t ||xp_u - xp_v||) -> [E].
+    rows = (r0, r1): (rowptr, col) is the rebased CSR slice of a row shard (parallel.csr_rows), xp every node's -> [E_loc]"""
     xp = _chk(xp)
     p = torch.empty((col.shape[0],), device=xp.device, dtype=torch.float32)
+    if rows is not None:
+        r0, n = _rows_of(rowptr, rows, "csr_uvdist_fwd")
+        if p.numel():
+            _lib.check(_lib.lib().dgg_csr_uvdist_fwd_rows(_ptr(xp), _ptr(rowptr), _ptr(col), r0, n, xp.shape[0], xp.shape[1], float(t), _ptr(p),
+                                                          _stream()), "csr_uvdist_fwd_rows")
+        return p
     _lib.check(_lib.lib().dgg_csr_uvdist_fwd(_ptr(xp), _ptr(rowptr), _ptr(col), xp.shape[0], xp.shape[1], float(t), _ptr(p), _stream()),
                "csr_uvdist_fwd")
     return p
 
 
-def csr_uvdist_bwd(xp, rowptr, col, p, dp, t=T_DIST):
+def csr_uvdist_bwd(xp, rowptr, col, p, dp, t=T_DIST, rows=None):
+    """-> dxp [N,h]; rows = (r0, r1): the share of a row shard's slice (the shards' shares sum to the whole gradient)"""
     xp = _chk(xp)
     dxp = _zeros(tuple(xp.shape), xp.device)
+    if rows is not None:
+        r0, n = _rows_of(rowptr, rows, "csr_uvdist_bwd")
+        if p.numel():
+            _lib.check(_lib.lib().dgg_csr_uvdist_bwd_rows(_ptr(xp), _ptr(rowptr), _ptr(col), r0, n, xp.shape[0], xp.shape[1], float(t),
+                                                          _ptr(_chk(p)), _ptr(_chk(dp)), _ptr(dxp), _stream()), "csr_uvdist_bwd_rows")
+        return dxp
     _lib.check(_lib.lib().dgg_csr_uvdist_bwd(_ptr(xp), _ptr(rowptr), _ptr(col), xp.shape[0], xp.shape[1], float(t), _ptr(_chk(p)),
                                              _ptr(_chk(dp)), _ptr(dxp), _stream()), "csr_uvdist_bwd")
     return dxp
@@ -1001,6 +1052,36 @@ def csr_norm_bwd(rowptr, col, w, rs, dA):
     dw = torch.empty_like(w)
     _lib.check(_lib.lib().dgg_csr_norm_bwd(_ptr(rowptr), _ptr(col), _ptr(_chk(w)), _ptr(_chk(rs)), _ptr(_chk(dA)), rs.shape[0], _ptr(da),
                                            _ptr(dw), _stream()), "csr_norm_bwd")
+    return dw
+
+
+def csr_normalize_fwd_rows(rowptr, col, w, rs, rows):
+    """normalize_adj on a row shard's rebased CSR slice: rs [N] every node's row sums -> ahat [E_loc]"""
+    r0, n = _rows_of(rowptr, rows, "csr_normalize_fwd_rows")
+    ahat = torch.empty_like(w)
+    if w.numel():
+        _lib.check(_lib.lib().dgg_csr_normalize_fwd_rows(_ptr(rowptr), _ptr(col), _ptr(_chk(w)), _ptr(_chk(rs)), r0, n, rs.shape[0], _ptr(ahat),
+                                                         _stream()), "csr_normalize_fwd_rows")
+    return ahat
+
+
+def csr_norm_bwd_acc_rows(rowptr, col, w, rs, dA, rows):
+    """first half of csr_norm_bwd on a slice -> the slice's share of the workspace da [N] (the caller sums the shards' shares)"""
+    r0, n = _rows_of(rowptr, rows, "csr_norm_bwd_acc_rows")
+    da = torch.zeros(tuple(rs.shape), device=rs.device, dtype=torch.float32)     # (handed to a collective: not a pool slice)
+    if w.numel():
+        _lib.check(_lib.lib().dgg_csr_norm_bwd_acc_rows(_ptr(rowptr), _ptr(col), _ptr(_chk(w)), _ptr(_chk(rs)), _ptr(_chk(dA)), r0, n, rs.shape[0],
+                                                        _ptr(da), _stream()), "csr_norm_bwd_acc_rows")
+    return da
+
+
+def csr_norm_bwd_apply_rows(rowptr, col, rs, dA, da, rows):
+    """second half: da [N] summed over the shards -> dw [E_loc]"""
+    r0, n = _rows_of(rowptr, rows, "csr_norm_bwd_apply_rows")
+    dw = torch.empty_like(dA)
+    if dA.numel():
+        _lib.check(_lib.lib().dgg_csr_norm_bwd_apply_rows(_ptr(rowptr), _ptr(col), _ptr(_chk(rs)), _ptr(_chk(dA)), _ptr(_chk(da)), r0, n,
+                                                          rs.shape[0], _ptr(dw), _stream()), "csr_norm_bwd_apply_rows")
     return dw
 
 
