@@ -297,6 +297,23 @@ int dgg_edgelist_topk_p(const float *p_edge, int64_t N, const int64_t *rowptr, c
 int dgg_edgelist_topk_p_rows(const float *p_edge, int64_t N, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
                              int noise_mode, const float *G, int64_t ldG, uint32_t s0, uint32_t s1, int K, int32_t *idx, float *val,
                              int32_t *eid, void *stream);
+/* The scorers that read nothing but the two end nodes and their degrees -- u-v-deg (dgm.py:1645-1670), u-v-deg-dist (1671-1702),
+ * edge_conv (1703-1719) -- on ALL-PAIRS candidates: score, perturbation (dgm.py:1211-1229) and torch.sort (dgm.py:1404) kept to the K
+ * best of rows [row0, row1), in one kernel; the N x N probabilities never exist.  Same bits as dgg_edge_mlp_fwd + dgg_edgelist_topk_p on
+ * the complete pattern (row i lists columns 0..N-1, self included; ties: lower column first).  AB [N,2*hw] and xp [N,h] hold every node
+ * (AB 16-byte aligned; xp is read for ex_mode 2 only); deg [N] (nullable: edge_conv) = the prior degrees that stand for the row sums of
+ * in_adj; ex_mode 0 or 2, act, weights as dgg_edge_mlp_fwd.  noise_mode DGG_NOISE_NONE / EXPLICIT / HASH / HASH_SYM; G is indexed as
+ * dgg_allpairs_topk indexes it: G[i * ldG + j] with i the GLOBAL row, ldG >= N.  idx / val / ex_out (nullable) [row1-row0, K] are
+ * OVERWRITTEN on every entry of the range and nothing else is written: empty ranks (N < K) are idx = -1, val = 0, ex_out = 0; ex_out =
+ * the extra of each selected entry (0 for ex_mode 0), which dgg_edge_mlp_bwd reads with eid = the entry's slot index.
+ * DGG_ERR_UNSUPPORTED and nothing written: hw or h outside {16, 32, 64, 128}, K > 64, ex_mode 1 (a per-edge array does not exist here),
+ * DGG_NOISE_RANKED / RANKED_SYM.  DGG_ERR_ARG and nothing written: missing inputs or weights, DGG_NOISE_EXPLICIT without G or with
+ * ldG < N, AB not 16-byte aligned, ex_mode / act / noise_mode outside their values, rows outside 0 <= row0 <= row1 <= N < 2^31.
+ * row0 == row1 returns 0 without a launch. */
+int dgg_allpairs_mlp_topk(const float *AB, const float *xp, int64_t N, int h, int hw, int64_t row0, int64_t row1, const float *deg,
+                          int ex_mode, float t_ex, const float *wdu, const float *wdv, const float *wex, const float *b1,
+                          const float *w2, const float *b2, int act, int noise_mode, const float *G, int64_t ldG, uint32_t s0,
+                          uint32_t s1, int K, int32_t *idx, float *val, float *ex_out, void *stream);
 /* autograd of dgg_edge_mlp_fwd for the selected entries: dval (wrt the stored score) -> dAB [N,2*hw] and
  * dpar [5*hw+1] = [dwdu | dwdv | dwex | db1 | dw2 | db2] (both ACCUMULATED into: caller zeroes), dex [N,K] (nullable,
  * overwritten; gradient wrt the per-edge extra).  ex [E] as written by the forward (nullable when ex_mode was 0). */

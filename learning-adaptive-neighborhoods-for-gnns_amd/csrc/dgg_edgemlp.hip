@@ -7,14 +7,13 @@
 // in exactly the operation order of oracle/dgg_oracle.c (mlp_edge_p).  The scorer writes one probability per candidate
 // edge; perturbation + top-K (edgelist_topk_p) and the soft top-k are shared with the u-v-dist path.
 #include "dgg_common.h"
+#include "dgg_edgemlp_score.h"
 #include <stdlib.h>
 #include "dgg_api_internal.h"
 
 using namespace dgg;
 
 namespace {
-
-__device__ __forceinline__ float act_apply(float z, int act) { return act == 1 ? (z > 0.0f ? z : __fmul_rn(0.01f, z)) : z; }
 
 // ---- forward: one thread per candidate edge --------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void edge_mlp_fwd_kernel(
@@ -30,18 +29,14 @@ __global__ __launch_bounds__(256) void edge_mlp_fwd_kernel(
     if (ex_mode == 1) {
         ex = ex_in[e];
     } else if (ex_mode == 2) {                                    // exp(t ||xp_u - xp_v||), canonical chain (dgm.py:1684-1686)
-        ex = c_exp(__fmul_rn(t_ex, c_sqrt(pair_d2_thread(xp + u * h, xp + v * h, h))));
+        ex = edge_mlp_dist_extra(xp + u * h, xp + v * h, h, t_ex);
     }
     if (ex_out) ex_out[e] = ex;
     const float *A = AB + u * 2 * hw, *B = AB + v * 2 * hw + hw;
     const float du = deg ? deg[u] : 0.0f, dv = deg ? deg[v] : 0.0f;
     float s = 0.0f;
     auto term = [&](float a, float b, int o) {                     // (one hidden unit; the sum over o stays in the oracle's order)
-        float z = __fadd_rn(a, b);
-        if (deg) { z = __fmaf_rn(du, wdu[o], z); z = __fmaf_rn(dv, wdv[o], z); }
-        if (ex_mode != 0) z = __fmaf_rn(ex, wex[o], z);
-        z = __fadd_rn(z, b1[o]);
-        s = __fmaf_rn(act_apply(z, act), w2[o], s);
+        s = edge_mlp_unit(a, b, o, deg != nullptr, du, dv, wdu, wdv, ex_mode != 0, ex, wex, b1, w2, act, s);
     };
     if ((hw & 15) == 0 && (reinterpret_cast<uintptr_t>(AB) & 15) == 0) {
         // 16-byte loads, sixteen hidden units (8 loads) in flight: a thread's two rows are its own cache lines, and one 4-byte load per
@@ -62,8 +57,7 @@ __global__ __launch_bounds__(256) void edge_mlp_fwd_kernel(
     } else {
         for (int o = 0; o < hw; o++) term(A[o], B[o], o);
     }
-    s = __fadd_rn(s, b2[0]);
-    p_edge[e] = __fdiv_rn(1.0f, __fadd_rn(1.0f, c_exp(-s)));
+    p_edge[e] = edge_mlp_prob(s, b2[0]);
 }
 
 // ---- perturbation + per-row top-K on given edge probabilities: one wavefront per row ----------------------------------
@@ -86,7 +80,7 @@ __global__ __launch_bounds__(256) void edgelist_topk_p_kernel(
             if (noise_mode != 0) {
                 const int32_t j = col[e];
                 const float g = noise_mode == 1 ? G[i * ldG + j] : pair_noise(s0, s1, (uint32_t)(row0 + i), (uint32_t)j, sym);
-                v = c_exp(__fadd_rn(c_log(__fadd_rn(v, 1e-8f)), g));
+                v = perturb_p(v, g);
             }
             key = make_key(v, (int32_t)(e - e0));
         }

@@ -264,6 +264,46 @@ class _DGGEdgeMlpAdjFn(torch.autograd.Function):
                 g(wex, 2 * hw, 3 * hw), dpar[3 * hw:4 * hw], dpar[4 * hw:5 * hw], dpar[5 * hw:5 * hw + 1], None)
 
 
+class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
+    """_DGGEdgeMlpAdjFn on ALL-PAIRS candidates (scorers u-v-deg / u-v-deg-dist / edge_conv, which read the two end nodes and their
+    prior degrees only): the scorer, the perturbation and the top-K run as one kernel over the complete candidate pattern
+    (dgg_allpairs_mlp_topk; no [N,N] array), with the bits of edge_mlp_fwd + edgelist_topk_p on that pattern.  From the 64-rank list
+    on everything is the edge-list node's code: the ramp, and the backward on the ELL block with eid = the slot index into the
+    per-entry extras the kernel returned."""
+
+    @staticmethod
+    def forward(ctx, x, k, deg, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
+        xp = ops.linear_fwd(x, We, be, ops.ACT_LEAKY)
+        AB = ops.linear_fwd(xp, Wcat, None, ops.ACT_NONE)
+        sdeg = deg if wdu is not None else None
+        idx, val, ex = ops.allpairs_mlp_topk(AB, xp, sdeg, cfg["ex_mode"], cfg["t_ex"], wdu, wdv, wex, eb1, w2, b2, cfg["act"], cfg["K"],
+                                             cfg["noise_mode"], cfg["G"], cfg["seed"])
+        w, rs = ops.softk_fwd(idx, val, k, cfg.get("fwd_mode", cfg["mode"]))
+        ctx.cfg = cfg
+        ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in (sdeg, ex, wdu, wdv, wex))
+        ctx.save_for_backward(x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2)
+        ctx.mark_non_differentiable(idx, val, rs)
+        return w, idx, val, rs
+
+    @staticmethod
+    def backward(ctx, dw, *_):
+        x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2 = ctx.saved_tensors
+        sdeg, ex, wdu, wdv, wex = ctx.opt
+        cfg = ctx.cfg
+        hw = Wcat.shape[0] // 2
+        eid = torch.arange(idx.numel(), device=idx.device, dtype=torch.int32).view_as(idx)     # (ex is [N,K]: an entry's extra is at its slot)
+        dval, dk = ops.softk_bwd(idx, val, k, dw.contiguous(), mode=cfg["mode"], normalized=False)
+        dAB, dpar, dex = ops.edge_mlp_bwd(AB, idx, eid, val, dval, sdeg, None if ex is None else ex.reshape(-1), wdu, wdv, wex, eb1, w2, b2,
+                                          cfg["act"], cfg["noise_mode"] != ops.NOISE_NONE, need_dex=cfg["ex_mode"] == 2)
+        dxp, dWcat, _ = ops.linear_bwd(xp, Wcat, AB, dAB, ops.ACT_NONE, need_dx=True, need_db=False)
+        if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
+            dxp = dxp + ops.edge_bwd(xp, idx, val, dex, t=cfg["t_ex"], perturb=False)
+        dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
+        g = lambda t_, a, b: None if t_ is None else dpar[a:b]  # noqa: E731
+        return (dx, dk, None, dWe, dbe, dWcat if ctx.needs_input_grad[5] else None, g(wdu, 0, hw), g(wdv, hw, 2 * hw),
+                g(wex, 2 * hw, 3 * hw), dpar[3 * hw:4 * hw], dpar[4 * hw:5 * hw], dpar[5 * hw:5 * hw + 1], None)
+
+
 class _DGGScoresFn(torch.autograd.Function):
     """Raw edge probabilities on the stored entries of in_adj, CSR order (reference edge_prob_net, dgm.py:1607-1725), for the
     forward variants that return them as the adjacency: debug_step 0 / 1 (dgm.py:1202-1209, 1240-1246) and the k-select mode
@@ -315,6 +355,7 @@ class _DGGScoresFn(torch.autograd.Function):
 
 _PAD_CACHE = {}
 _EDGE_MLP_FUSED = ("u-v-deg", "u-v-A_uv", "u-v-deg-dist", "edge_conv", "A_uv")     # edge-MLP scorers the fused layer covers
+_EDGE_MLP_ALLPAIRS = ("u-v-deg", "u-v-deg-dist", "edge_conv")     # ... that read the end nodes and their degrees only: all-pairs candidates
 
 
 def _pad_features(x, params, keys):
@@ -875,12 +916,14 @@ class DGG_LearnableK_debug(nn.Module):
           "csr_when_needed"  the CSR form from the forward whose learned degrees first need it, and from then on (auto on edge lists
                              and for explicit noise tensors on small all-pairs graphs; csr_auto)
           "list"             64 ranks per row, the bound enforced by check_ell_bound (ell; graphs beyond dgg_allpairs_csr_max without a
-                             chunked form)"""
+                             chunked form; the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv on all-pairs candidates)"""
         policy = getattr(self.args, "dgg_wide_rows", "auto")
         if not all_pairs:
             return {"ell": "list", "csr": "csr"}.get(policy, "csr_when_needed")
         if self._chunk_policy(noise_mode):
             return "chunked"
+        if self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS:     # (the edge-MLP scorers on all-pairs candidates have the list only)
+            return "list"
         if policy in ("ell", "chunked") or N > int(getattr(self.args, "dgg_allpairs_csr_max", 8192)):
             return "list"
         return "csr" if policy == "csr" else "csr_when_needed"
@@ -1149,9 +1192,15 @@ class DGG_LearnableK_debug(nn.Module):
             return self._scores_adjacency(x, in_adj)
         avals = erow = None
         if isinstance(in_adj, AllPairs):
-            if self.edge_prob_net_mode != "u-v-dist":
-                raise NotImplementedError("all-pairs candidates are defined for 'u-v-dist' only (the other scorers read "
-                                          "per-edge features of in_adj, dgm.py:1628-1725)")
+            if self.edge_prob_net_mode != "u-v-dist" and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS:
+                raise NotImplementedError(f"all-pairs candidates are defined for 'u-v-dist' and the edge-MLP scorers {_EDGE_MLP_ALLPAIRS} "
+                                          f"only: {self.edge_prob_net_mode!r} reads the stored values of in_adj (dgm.py:1628-1644, "
+                                          "1720-1725), which all-pairs candidates do not have")
+            if self.edge_prob_net_mode != "u-v-dist" and (
+                    self.latent_dim not in (16, 32, 64, 128) or (self.edge_prob_net_mode == "edge_conv" and self.latent_dim == 16) or self.ell_width > 64):
+                # (the widths dgg_allpairs_mlp_topk is built for; edge_conv's hidden width is latent_dim / 2)
+                raise NotImplementedError(f"edge-MLP scorers {_EDGE_MLP_ALLPAIRS} on all-pairs candidates: latent_dim in (16, 32, 64, 128) "
+                                          "(edge_conv: from 32), ell_width <= 64")
             cand, deg = None, in_adj.prior_degree
         else:
             if isinstance(in_adj, EllAdjacency):     # dgg_adj_input != "input_adj": previous learned graph
@@ -1163,11 +1212,12 @@ class DGG_LearnableK_debug(nn.Module):
                 erow, avals = in_adj.indices()[0].to(torch.int32), in_adj.values().to(torch.float32)
         noise_mode, G, seed = self._noise_cfg()
         literal = bool(self.hard and getattr(self.args, "dgg_hard_literal", False))
-        if noise_mode == ops.NOISE_RANKED and cand is None and not literal:
+        ap_mlp = cand is None and self.edge_prob_net_mode != "u-v-dist"     # edge-MLP scorer on all-pairs candidates: every pair is scored
+        if noise_mode == ops.NOISE_RANKED and cand is None and not literal and not ap_mlp:
             noise_mode = self._asym_generator_now(x, seed)       # the ranked search's depth is a property of the data: guarded
-        if noise_mode == ops.NOISE_RANKED_SYM and (cand is not None or literal):
+        if noise_mode == ops.NOISE_RANKED_SYM and (cand is not None or literal or ap_mlp):
             noise_mode = ops.NOISE_HASH_SYM
-        if noise_mode == ops.NOISE_RANKED and (cand is not None or literal):
+        if noise_mode == ops.NOISE_RANKED and (cand is not None or literal or ap_mlp):
             noise_mode = ops.NOISE_HASH              # edge-list candidates: every candidate is scored, per-pair hash noise
                                                      # (literal dgg_hard: the full ranking of a row needs per-pair noise as well)
         cfg = dict(cand=cand, K=self.ell_width, t=ops.T_DIST, noise_mode=noise_mode, G=G, seed=seed, algo=self.topk_algo,
@@ -1175,7 +1225,8 @@ class DGG_LearnableK_debug(nn.Module):
                    mode=ops.MODE_K_TIMES_EDGE_PROB if self.k_select_mode == "k_times_edge_prob" else ops.MODE_K_ONLY)
         if literal and (self.edge_prob_net_mode != "u-v-dist" or x.shape[0] > 8192):
             raise NotImplementedError("dgg_hard_literal: the literal return_hard_or_soft needs the full ranking of every row's N scores "
-                                      "(u-v-dist scorer, N <= 8192); use the default straight-through dgg_hard otherwise")
+                                      "(u-v-dist scorer, N <= 8192); use the default straight-through dgg_hard otherwise (edge lists, "
+                                      f"and all-pairs candidates under 'u-v-dist' or {_EDGE_MLP_ALLPAIRS})")
         if self.hard and cfg["mode"] == ops.MODE_K_TIMES_EDGE_PROB and not literal:
             # dgg_hard: straight-through adjacency `(hard - soft).detach() + soft` with hard = the ramp mask at the selected
             # columns (the SDD class's definition, dgm.py:343-346; for k_only hard == soft).  The debug class's own
@@ -1189,7 +1240,8 @@ class DGG_LearnableK_debug(nn.Module):
             xp_dual, xk = self._project_for_k(x, literal)
             if self.k_net_mode == "gcn-x-deg":       # relu(normalize_adj(in_adj) @ xk @ k_W)   (dgm.py:1528-1540)
                 if cand is None:
-                    raise NotImplementedError("k-net mode 'gcn-x-deg' aggregates over the stored entries of in_adj")
+                    raise NotImplementedError("k-net mode 'gcn-x-deg' aggregates over the stored entries of in_adj, which all-pairs candidates "
+                                              "do not have (k-net modes 'x', 'input_deg', 'learn_normalized_degree' run on them)")
                 pat = csr_pattern(in_adj)
                 nadj = CsrAdjacency(pat[0], pat[1], pat[2], in_adj.coalesce().values().float(), x.shape[0]).normalize()
                 xk = ops.LinearFn.apply(nadj.matmul(xk), self.k_W, None, ops.ACT_RELU, 1)
@@ -1238,6 +1290,11 @@ class DGG_LearnableK_debug(nn.Module):
         elif self.edge_prob_net_mode == "u-v-dist":
             cfg["want_bwd"] = ops.backward_will_follow(x, k, We, be)
             w, idx, val, rs = _DGGSoftAdjFn.apply(x, k, We, be, cfg)
+        elif cand is None:                       # u-v-deg / u-v-deg-dist / edge_conv on all-pairs candidates: the prior degrees are the degrees
+            mlp, _ = self._edge_mlp_terms(None)
+            cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
+            w, idx, val, rs = _DGGAllPairsMlpAdjFn.apply(x, k, deg, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"],
+                                                         mlp["w2"], mlp["b2"], cfg)
         else:
             mlp, ex_in = self._edge_mlp_terms(avals)
             cfg.update(cand=(rowptr, col, erow), ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])

@@ -683,6 +683,36 @@ def edgelist_topk_p(p_edge, N, rowptr, col, K=DEFAULT_K, noise_mode=NOISE_NONE, 
     return idx, val, eid
 
 
+def allpairs_mlp_topk(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act=ACT_LEAKY, K=DEFAULT_K, noise_mode=NOISE_NONE, G=None,
+                      seed=(0, 0), rows=None, out=None):
+    """edge-MLP scorer (u-v-deg / u-v-deg-dist / edge_conv) + perturbation + per-row top-K on ALL-PAIRS candidates in one kernel
+    (dgg_allpairs_mlp_topk): the bits of edge_mlp_fwd + edgelist_topk_p on the complete pattern, without its N^2 arrays
+    -> idx, val [r1-r0, K], ex [r1-r0, K] (the extra of each selected entry; None for ex_mode 0).
+    deg [N] (None: edge_conv) = the prior degrees; rows = (r0, r1): those rows only (AB, xp, deg stay every node's, G stays [N, N]).
+    out = (idx, val, ex): write into these tensors (tests: canaried buffers) instead of fresh ones."""
+    AB, xp = _chk(AB), _chk(xp)
+    N, h = xp.shape
+    hw = AB.shape[1] // 2
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    if out is None:
+        n = max(r1 - r0, 0)
+        idx = torch.empty((n, K), device=xp.device, dtype=torch.int32)
+        val = torch.empty((n, K), device=xp.device, dtype=torch.float32)
+        ex = torch.empty((n, K), device=xp.device, dtype=torch.float32) if ex_mode else None
+    else:
+        idx, val, ex = out
+    ldG = 0
+    if G is not None:
+        G = _chk(G)
+        ldG = G.shape[-1]
+    o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
+    _lib.check(_lib.lib().dgg_allpairs_mlp_topk(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
+                                                _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act, noise_mode,
+                                                _ptr(G), ldG, seed[0], seed[1], K, _ptr(idx), _ptr(val), _ptr(ex), _stream()),
+               "allpairs_mlp_topk")
+    return idx, val, ex
+
+
 def edge_mlp_bwd(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, act=ACT_LEAKY, perturb=False, need_dex=False,
                  rowptr=None, partp=None, w=None, nrec_max=0, rows=None):
     """-> dAB [N,2hw], dpar [5hw+1] = [dwdu|dwdv|dwex|db1|dw2|db2], dex (shape of dval) or None.
