@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import ops
 from .adjacency import AllPairs, CsrAdjacency, EllAdjacency, _cached, csr_candidates, csr_pattern, csr_pattern_rows
+from .parallel import edge_mlp_score_bwd, uvdist_score_bwd
 
 _EDGE_MLP_MODES = ("u-v-A_uv", "u-v-deg", "u-v-deg-dist", "edge_conv", "A_uv")
 
@@ -124,36 +125,42 @@ class _DualProjFn(torch.autograd.Function):
         return dx, dW[:h1], db[:h1], dW[h1:], db[h1:]
 
 
+def _soft_adj_fwd(ctx, xp, k, cfg):
+    """u-v-dist scoring + perturbation + top-K + ramp on a projected xp -> w, idx, val, rs; leaves the destination-ordered partition of the
+    active entries in cfg["part"] (the column-side terms of the backward run on it instead of entry-wise float atomics; built only when a
+    backward can follow)"""
+    if cfg["cand"] is None:
+        idx, val = ops.allpairs_topk(xp, cfg["K"], cfg["t"], cfg["noise_mode"], cfg["G"], cfg["seed"], algo=cfg["algo"],
+                                     k_limit=k, status=cfg)
+    else:
+        rowptr, col = cfg["cand"]
+        idx, val = ops.edgelist_topk(xp, rowptr, col, cfg["K"], cfg["t"], cfg["noise_mode"], cfg["G"], cfg["seed"])
+    w, rs = ops.softk_fwd(idx, val, k, cfg.get("fwd_mode", cfg["mode"]))
+    ctx.cfg = cfg
+    cfg["part"] = ops.part_build(idx, w, xp.shape[0]) if cfg.get("want_bwd", any(ctx.needs_input_grad)) else None
+    ctx.mark_non_differentiable(idx, val, rs)
+    return w, idx, val, rs
+
+
+def _soft_adj_bwd(cfg, xp, k, idx, val, dw):
+    """-> dxp, dk of _soft_adj_fwd"""
+    return uvdist_score_bwd(ops, xp, idx, val, k, dw.contiguous(), None, None, 0, cfg["t"], cfg["noise_mode"] != ops.NOISE_NONE,
+                            cfg["mode"], False, cfg.get("part"))
+
+
 class _DGGSoftAdjXpFn(torch.autograd.Function):
     """_DGGSoftAdjFn on an already projected xp (see _DualProjFn): u-v-dist scoring + perturbation + top-K + ramp; the gradient
     goes back to xp."""
 
     @staticmethod
     def forward(ctx, xp, k, cfg):
-        if cfg["cand"] is None:
-            idx, val = ops.allpairs_topk(xp, cfg["K"], cfg["t"], cfg["noise_mode"], cfg["G"], cfg["seed"], algo=cfg["algo"],
-                                         k_limit=k, status=cfg)
-        else:
-            rowptr, col = cfg["cand"]
-            idx, val = ops.edgelist_topk(xp, rowptr, col, cfg["K"], cfg["t"], cfg["noise_mode"], cfg["G"], cfg["seed"])
-        w, rs = ops.softk_fwd(idx, val, k, cfg.get("fwd_mode", cfg["mode"]))
-        ctx.cfg = cfg
-        cfg["part"] = ops.part_build(idx, w, xp.shape[0]) if cfg.get("want_bwd", any(ctx.needs_input_grad)) else None
-        ctx.save_for_backward(xp, k, idx, val)
-        ctx.mark_non_differentiable(idx, val, rs)
-        return w, idx, val, rs
+        out = _soft_adj_fwd(ctx, xp, k, cfg)
+        ctx.save_for_backward(xp, k, out[1], out[2])
+        return out
 
     @staticmethod
     def backward(ctx, dw, *_):
-        xp, k, idx, val = ctx.saved_tensors
-        cfg = ctx.cfg
-        fused = ops.softk_edge_bwd(xp, idx, val, k, dw.contiguous(), t=cfg["t"], perturb=cfg["noise_mode"] != ops.NOISE_NONE,
-                                   mode=cfg["mode"], normalized=False, part=cfg.get("part"))
-        if fused is not None:
-            dxp, dk, _ = fused
-        else:
-            dval, dk = ops.softk_bwd(idx, val, k, dw.contiguous(), mode=cfg["mode"], normalized=False)
-            dxp = ops.edge_bwd(xp, idx, val, dval, t=cfg["t"], perturb=cfg["noise_mode"] != ops.NOISE_NONE, part=cfg.get("part"))
+        dxp, dk = _soft_adj_bwd(ctx.cfg, *ctx.saved_tensors, dw)
         return dxp, dk, None
 
 
@@ -188,39 +195,37 @@ class _DGGWideAdjFn(torch.autograd.Function):
 
 class _DGGSoftAdjFn(torch.autograd.Function):
     """x, learned k, projection parameters -> soft (unnormalised) ELL adjacency values: projection, u-v-dist scoring +
-    perturbation + top-K, ramp (reference dgm.py:1197-1292)."""
+    perturbation + top-K, ramp (reference dgm.py:1197-1292): _DGGSoftAdjXpFn plus the projection."""
 
     @staticmethod
     def forward(ctx, x, k, We, be, cfg):
         xp = ops.linear_fwd(x, We, be, ops.ACT_LEAKY)
-        if cfg["cand"] is None:
-            idx, val = ops.allpairs_topk(xp, cfg["K"], cfg["t"], cfg["noise_mode"], cfg["G"], cfg["seed"], algo=cfg["algo"],
-                                         k_limit=k, status=cfg)
-        else:
-            rowptr, col = cfg["cand"]
-            idx, val = ops.edgelist_topk(xp, rowptr, col, cfg["K"], cfg["t"], cfg["noise_mode"], cfg["G"], cfg["seed"])
-        w, rs = ops.softk_fwd(idx, val, k, cfg.get("fwd_mode", cfg["mode"]))
-        ctx.cfg = cfg
-        # destination-ordered partition of the active entries: the column-side terms of the backward run on it instead of
-        # entry-wise float atomics (built only when a backward can follow)
-        cfg["part"] = ops.part_build(idx, w, x.shape[0]) if cfg.get("want_bwd", any(ctx.needs_input_grad)) else None
-        ctx.save_for_backward(x, We, xp, k, idx, val)
-        ctx.mark_non_differentiable(idx, val, rs)
-        return w, idx, val, rs
+        out = _soft_adj_fwd(ctx, xp, k, cfg)
+        ctx.save_for_backward(x, We, xp, k, out[1], out[2])
+        return out
 
     @staticmethod
     def backward(ctx, dw, *_):
         x, We, xp, k, idx, val = ctx.saved_tensors
-        cfg = ctx.cfg
-        fused = ops.softk_edge_bwd(xp, idx, val, k, dw.contiguous(), t=cfg["t"], perturb=cfg["noise_mode"] != ops.NOISE_NONE,
-                                   mode=cfg["mode"], normalized=False, part=cfg.get("part"))
-        if fused is not None:
-            dxp, dk, _ = fused
-        else:
-            dval, dk = ops.softk_bwd(idx, val, k, dw.contiguous(), mode=cfg["mode"], normalized=False)
-            dxp = ops.edge_bwd(xp, idx, val, dval, t=cfg["t"], perturb=cfg["noise_mode"] != ops.NOISE_NONE, part=cfg.get("part"))
+        dxp, dk = _soft_adj_bwd(ctx.cfg, xp, k, idx, val, dw)
         dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
         return dx, dk, dWe, dbe, None
+
+
+_SC_KEYS = ("Wcat", "wdu", "wdv", "wex", "b1", "w2", "b2")      # the edge-MLP scorer's terms, in the order the nodes take them
+
+
+def _mlp_score_bwd(ctx, terms, xp, AB, idx, eid, val, dval, ex, perturb, i_wcat, **kw):
+    """edge-MLP scorer backward of the three nodes below from d loss / d score (parallel.edge_mlp_score_bwd) -> dxp without the distance
+    term, dex, the gradients of the scorer's terms in node order (Wcat's only if input `i_wcat` needs one).  terms = the saved (Wcat,
+    b1, w2, b2); the optional ones are in ctx.opt."""
+    sdeg, _, wdu, wdv, wex = ctx.opt
+    Wcat, eb1, w2, b2 = terms
+    sc = dict(Wcat=Wcat, wdu=wdu, wdv=wdv, wex=wex, b1=eb1, w2=w2, b2=b2, act=ctx.cfg["act"], ex_mode=ctx.cfg["ex_mode"])
+    dxp, dex, gs = edge_mlp_score_bwd(ops, sc, xp, AB, idx, eid, val, dval, sdeg, ex, perturb, **kw)
+    if not ctx.needs_input_grad[i_wcat]:
+        gs["Wcat"] = None
+    return dxp, dex, tuple(gs[k_] for k_ in _SC_KEYS)
 
 
 class _DGGEdgeMlpAdjFn(torch.autograd.Function):
@@ -248,20 +253,14 @@ class _DGGEdgeMlpAdjFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dw, *_):
-        x, We, xp, k, idx, val, eid, AB, Wcat, eb1, w2, b2 = ctx.saved_tensors
-        sdeg, ex, wdu, wdv, wex = ctx.opt
+        x, We, xp, k, idx, val, eid, AB, *terms = ctx.saved_tensors
         cfg = ctx.cfg
-        hw = Wcat.shape[0] // 2
         dval, dk = ops.softk_bwd(idx, val, k, dw.contiguous(), mode=cfg["mode"], normalized=False)
-        dAB, dpar, dex = ops.edge_mlp_bwd(AB, idx, eid, val, dval, sdeg, ex, wdu, wdv, wex, eb1, w2, b2, cfg["act"],
-                                          cfg["noise_mode"] != ops.NOISE_NONE, need_dex=cfg["ex_mode"] == 2)
-        dxp, dWcat, _ = ops.linear_bwd(xp, Wcat, AB, dAB, ops.ACT_NONE, need_dx=True, need_db=False)
+        dxp, dex, gsc = _mlp_score_bwd(ctx, terms, xp, AB, idx, eid, val, dval, ctx.opt[1], cfg["noise_mode"] != ops.NOISE_NONE, 6)
         if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
             dxp = dxp + ops.edge_bwd(xp, idx, val, dex, t=cfg["t_ex"], perturb=False)
         dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
-        g = lambda t_, a, b: None if t_ is None else dpar[a:b]  # noqa: E731
-        return (dx, dk, None, None, dWe, dbe, dWcat if ctx.needs_input_grad[6] else None, g(wdu, 0, hw), g(wdv, hw, 2 * hw),
-                g(wex, 2 * hw, 3 * hw), dpar[3 * hw:4 * hw], dpar[4 * hw:5 * hw], dpar[5 * hw:5 * hw + 1], None)
+        return (dx, dk, None, None, dWe, dbe) + gsc + (None,)
 
 
 class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
@@ -287,21 +286,16 @@ class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dw, *_):
-        x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2 = ctx.saved_tensors
-        sdeg, ex, wdu, wdv, wex = ctx.opt
+        x, We, xp, k, idx, val, AB, *terms = ctx.saved_tensors
         cfg = ctx.cfg
-        hw = Wcat.shape[0] // 2
         eid = torch.arange(idx.numel(), device=idx.device, dtype=torch.int32).view_as(idx)     # (ex is [N,K]: an entry's extra is at its slot)
         dval, dk = ops.softk_bwd(idx, val, k, dw.contiguous(), mode=cfg["mode"], normalized=False)
-        dAB, dpar, dex = ops.edge_mlp_bwd(AB, idx, eid, val, dval, sdeg, None if ex is None else ex.reshape(-1), wdu, wdv, wex, eb1, w2, b2,
-                                          cfg["act"], cfg["noise_mode"] != ops.NOISE_NONE, need_dex=cfg["ex_mode"] == 2)
-        dxp, dWcat, _ = ops.linear_bwd(xp, Wcat, AB, dAB, ops.ACT_NONE, need_dx=True, need_db=False)
+        ex = None if ctx.opt[1] is None else ctx.opt[1].reshape(-1)
+        dxp, dex, gsc = _mlp_score_bwd(ctx, terms, xp, AB, idx, eid, val, dval, ex, cfg["noise_mode"] != ops.NOISE_NONE, 5)
         if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
             dxp = dxp + ops.edge_bwd(xp, idx, val, dex, t=cfg["t_ex"], perturb=False)
         dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
-        g = lambda t_, a, b: None if t_ is None else dpar[a:b]  # noqa: E731
-        return (dx, dk, None, dWe, dbe, dWcat if ctx.needs_input_grad[5] else None, g(wdu, 0, hw), g(wdv, hw, 2 * hw),
-                g(wex, 2 * hw, 3 * hw), dpar[3 * hw:4 * hw], dpar[4 * hw:5 * hw], dpar[5 * hw:5 * hw + 1], None)
+        return (dx, dk, None, dWe, dbe) + gsc + (None,)
 
 
 class _DGGScoresFn(torch.autograd.Function):
@@ -339,18 +333,12 @@ class _DGGScoresFn(torch.autograd.Function):
             dxp = ops.csr_uvdist_bwd(xp, rowptr, col, p, dp, cfg["t"], rows=rows)
             dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
             return (dx, None, None, dWe, dbe) + (None,) * 8
-        x, We, xp, p, AB, Wcat, eb1, w2, b2 = ctx.saved_tensors
-        sdeg, ex, wdu, wdv, wex = ctx.opt
-        hw = Wcat.shape[0] // 2
-        dAB, dpar, dex = ops.edge_mlp_bwd(AB, col, None, p, dp, sdeg, ex, wdu, wdv, wex, eb1, w2, b2, cfg["act"], False,
-                                          need_dex=cfg["ex_mode"] == 2, rowptr=rowptr, rows=rows)
-        dxp, dWcat, _ = ops.linear_bwd(xp, Wcat, AB, dAB, ops.ACT_NONE, need_dx=True, need_db=False)
+        x, We, xp, p, AB, *terms = ctx.saved_tensors
+        dxp, dex, gsc = _mlp_score_bwd(ctx, terms, xp, AB, col, None, p, dp, ctx.opt[1], False, 5, rowptr=rowptr, rows=rows)
         if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
-            dxp = dxp + ops.csr_uvdist_bwd(xp, rowptr, col, ex, dex, cfg["t_ex"], rows=rows)
+            dxp = dxp + ops.csr_uvdist_bwd(xp, rowptr, col, ctx.opt[1], dex, cfg["t_ex"], rows=rows)
         dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
-        g = lambda t_, a, b: None if t_ is None else dpar[a:b]  # noqa: E731
-        return (dx, None, None, dWe, dbe, dWcat if ctx.needs_input_grad[5] else None, g(wdu, 0, hw), g(wdv, hw, 2 * hw),
-                g(wex, 2 * hw, 3 * hw), dpar[3 * hw:4 * hw], dpar[4 * hw:5 * hw], dpar[5 * hw:5 * hw + 1], None)
+        return (dx, None, None, dWe, dbe) + gsc + (None,)
 
 
 _PAD_CACHE = {}
@@ -400,6 +388,65 @@ def _unpad_grads(g, keys, d):
 PAD_ODD_FEATURES = __import__("os").environ.get("DGG_PAD_ODD_FEATURES", "1") != "0"
 
 
+def _fused_fwd(ctx, layer, x, deg, params, scorer=None):
+    """prologue of the two fused nodes: pad, replicated-feature slice, the engine's forward -> (Z, ahat) as fresh views.
+    scorer: the arguments of _pack_scorer (the edge-MLP node); packed after the padding, as the node always did."""
+    x, params, ctx.d_orig = _pad_features(x, params, layer.PARAM_KEYS)
+    if layer.x_full is not None:
+        # replicated features (dgg_amd.distributed): x holds every node, projected whole for the scoring side; the rest of the
+        # step reads the layer's own rows
+        layer.x_full, x = x, x[layer.r0:layer.r1]
+    ctx.x_full = layer.x_full
+    P = dict(zip(layer.PARAM_KEYS, params))
+    if scorer is not None:
+        ctx.packed, ctx.scorer = _pack_scorer(*scorer)
+        layer.scorer = ctx.scorer
+    # (layer.want_backward was set by forward_conv BEFORE .apply(): grad mode is always off in here, and ctx.needs_input_grad says
+    #  (True, ...) under torch.no_grad() too)
+    Z = layer.forward(x, deg, P)
+    ctx.layer, ctx.state = layer, layer.saved
+    ctx.save_for_backward(x, *params)
+    ctx.set_materialize_grads(False)
+    # second output: the NORMALISED adjacency values [N,K] -- differentiable, for the layers after this one that read the same
+    # adjacency (model.py:1266-1290); its cotangent joins the aggregation's own inside the backward.
+    # Both outputs leave as fresh VIEWS: autograd hangs this node on the returned objects, and the tensors kept in `saved` (which the
+    # node's ctx holds) must not be those objects -- output -> grad_fn -> ctx -> saved -> output is a reference cycle that only the
+    # cyclic collector frees, i.e. a step's whole state (gigabytes on chunked rows) stays allocated for an unbounded number of steps
+    return Z.view(Z.shape), layer.saved["ahat"].view(layer.saved["ahat"].shape)
+
+
+def _fused_bwd(ctx, dZ, dahat):
+    """epilogue of the two fused nodes: the engine back in the state of this node's forward, its backward -> the gradient dict, every
+    parameter's in the parameter's shape, unpadded"""
+    x, *params = ctx.saved_tensors
+    layer = ctx.layer
+    P = dict(zip(layer.PARAM_KEYS, params))
+    layer.saved, layer._fwd_gen = ctx.state, ctx.state["gen"]       # (another forward of the same module may have run since)
+    layer.x_full = ctx.x_full
+    layer.x_grad = bool(ctx.needs_input_grad[0])
+    if dZ is None:
+        dZ = torch.zeros_like(ctx.state["Z"])
+    g = layer.backward(dZ.contiguous(), x, P, dA_ext=dahat)
+    for k_ in layer.PARAM_KEYS:
+        g[k_] = g[k_].reshape(P[k_].shape)
+    return _unpad_grads(g, layer.PARAM_KEYS, ctx.d_orig)
+
+
+def _pack_scorer(sc_static, Wcat, wdu, wdv, wex, b1, w2, b2):
+    """-> (packed, the engine's scorer dict): the edge-MLP scorer's terms, detached"""
+    det = lambda t_: None if t_ is None else t_.detach()  # noqa: E731
+    packed = sc_static.get("packed")
+    if packed is not None:
+        # `Wcat` is edge_encode.0.weight [h, 2h + extras] itself (columns [u | v | extras], dgm.py:1101-1105): sliced here, outside
+        # autograd (the slices of the separate-modules path cost a dozen tiny copy / zero-fill launches per step in their backward)
+        h_, cols = packed
+        W0 = Wcat.detach()
+        pick = lambda c_: None if c_ is None else W0[:, c_].contiguous()  # noqa: E731
+        Wcat, wdu, wdv, wex = torch.cat([W0[:, :h_], W0[:, h_:2 * h_]], 0), pick(cols[0]), pick(cols[1]), pick(cols[2])
+        w2 = w2.detach().reshape(-1)
+    return packed, dict(sc_static, Wcat=det(Wcat), wdu=det(wdu), wdv=det(wdv), wex=det(wex), b1=det(b1), w2=det(w2), b2=det(b2))
+
+
 class _FusedDGGConvFn(torch.autograd.Function):
     """generator -> normalize_adj -> relu(A (x Wc)) as ONE autograd node on the hand-scheduled step of dgg_amd.parallel.ShardedDGGConv
     (reference dgm.py:1178-1292, model.py:1205-1219, 580-599): x is read ONCE for the three projections [xp | xk | x Wc] and once for
@@ -409,84 +456,27 @@ class _FusedDGGConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, deg, layer, *params):
-        x, params, ctx.d_orig = _pad_features(x, params, layer.PARAM_KEYS)
-        if layer.x_full is not None:
-            # replicated features (dgg_amd.distributed): x holds every node, projected whole for the scoring side; the rest of the
-            # step reads the layer's own rows
-            layer.x_full, x = x, x[layer.r0:layer.r1]
-        ctx.x_full = layer.x_full
-        P = dict(zip(layer.PARAM_KEYS, params))
-        # (layer.want_backward was set by forward_conv BEFORE .apply(): grad mode is always off in here, and ctx.needs_input_grad says
-        #  (True, ...) under torch.no_grad() too)
-        Z = layer.forward(x, deg, P)
-        ctx.layer, ctx.state = layer, layer.saved
-        ctx.save_for_backward(x, *params)
-        ctx.set_materialize_grads(False)
-        # second output: the NORMALISED adjacency values [N,K] -- differentiable, for the layers after this one that read the same
-        # adjacency (model.py:1266-1290); its cotangent joins the aggregation's own inside the backward.
-        # Both outputs leave as fresh VIEWS: autograd hangs this node on the returned objects, and the tensors kept in `saved` (which the
-        # node's ctx holds) must not be those objects -- output -> grad_fn -> ctx -> saved -> output is a reference cycle that only the
-        # cyclic collector frees, i.e. a step's whole state (gigabytes on chunked rows) stays allocated for an unbounded number of steps
-        return Z.view(Z.shape), layer.saved["ahat"].view(layer.saved["ahat"].shape)
+        return _fused_fwd(ctx, layer, x, deg, params)
 
     @staticmethod
     def backward(ctx, dZ, dahat):
-        x, *params = ctx.saved_tensors
-        layer = ctx.layer
-        P = dict(zip(layer.PARAM_KEYS, params))
-        layer.saved, layer._fwd_gen = ctx.state, ctx.state["gen"]       # (another forward of the same module may have run since)
-        layer.x_full = ctx.x_full
-        layer.x_grad = bool(ctx.needs_input_grad[0])
-        if dZ is None:
-            dZ = torch.zeros_like(ctx.state["Z"])
-        g = layer.backward(dZ.contiguous(), x, P, dA_ext=dahat)
-        for k_ in layer.PARAM_KEYS:
-            g[k_] = g[k_].reshape(P[k_].shape)
-        g = _unpad_grads(g, layer.PARAM_KEYS, ctx.d_orig)
-        return (g.get("x"), None, None) + tuple(g[k_] for k_ in layer.PARAM_KEYS)
+        g = _fused_bwd(ctx, dZ, dahat)
+        return (g.get("x"), None, None) + tuple(g[k_] for k_ in ctx.layer.PARAM_KEYS)
 
 
 class _FusedDGGMlpConvFn(torch.autograd.Function):
     """_FusedDGGConvFn with an edge-MLP scorer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv; reference dgm.py:1628-1719) on edge-list
     candidates: the scorer's terms arrive in the per-node / per-edge form of DGG_LearnableK_debug._edge_mlp_terms (sliced from the
     reference's parameters by differentiable torch ops outside this node) and get their gradients from the same backward."""
-    SC_KEYS = ("Wcat", "wdu", "wdv", "wex", "b1", "w2", "b2")
 
     @staticmethod
     def forward(ctx, x, deg, layer, sc_static, Wcat, wdu, wdv, wex, b1, w2, b2, *params):
-        x, params, ctx.d_orig = _pad_features(x, params, layer.PARAM_KEYS)
-        if layer.x_full is not None:                     # replicated features on a row shard (as in _FusedDGGConvFn.forward)
-            layer.x_full, x = x, x[layer.r0:layer.r1]
-        ctx.x_full = layer.x_full
-        P = dict(zip(layer.PARAM_KEYS, params))
-        det = lambda t_: None if t_ is None else t_.detach()  # noqa: E731
-        ctx.packed = packed = sc_static.get("packed")
-        if packed is not None:
-            # `Wcat` is edge_encode.0.weight [h, 2h + extras] itself (columns [u | v | extras], dgm.py:1101-1105): sliced here, outside
-            # autograd (the slices of the separate-modules path cost a dozen tiny copy / zero-fill launches per step in their backward)
-            h_, cols = packed
-            W0 = Wcat.detach()
-            pick = lambda c_: None if c_ is None else W0[:, c_].contiguous()  # noqa: E731
-            Wcat, wdu, wdv, wex = torch.cat([W0[:, :h_], W0[:, h_:2 * h_]], 0), pick(cols[0]), pick(cols[1]), pick(cols[2])
-            w2 = w2.detach().reshape(-1)
-        layer.scorer = dict(sc_static, Wcat=det(Wcat), wdu=det(wdu), wdv=det(wdv), wex=det(wex), b1=det(b1), w2=det(w2), b2=det(b2))
-        Z = layer.forward(x, deg, P)
-        ctx.layer, ctx.state, ctx.scorer = layer, layer.saved, layer.scorer
-        ctx.save_for_backward(x, *params)
-        ctx.set_materialize_grads(False)
-        return Z.view(Z.shape), layer.saved["ahat"].view(layer.saved["ahat"].shape)       # (fresh views: see _FusedDGGConvFn.forward)
+        return _fused_fwd(ctx, layer, x, deg, params, scorer=(sc_static, Wcat, wdu, wdv, wex, b1, w2, b2))
 
     @staticmethod
     def backward(ctx, dZ, dahat):
-        x, *params = ctx.saved_tensors
-        layer = ctx.layer
-        P = dict(zip(layer.PARAM_KEYS, params))
-        layer.saved, layer._fwd_gen, layer.scorer = ctx.state, ctx.state["gen"], ctx.scorer
-        layer.x_full = ctx.x_full
-        layer.x_grad = bool(ctx.needs_input_grad[0])
-        if dZ is None:
-            dZ = torch.zeros_like(ctx.state["Z"])
-        g = layer.backward(dZ.contiguous(), x, P, dA_ext=dahat)
+        ctx.layer.scorer = ctx.scorer
+        g = _fused_bwd(ctx, dZ, dahat)
         gs = g["scorer"]
         if ctx.packed is not None:                       # d loss / d edge_encode.0.weight in ONE concatenation
             hw = gs["Wcat"].shape[0] // 2
@@ -495,11 +485,8 @@ class _FusedDGGMlpConvFn(torch.autograd.Function):
             dW0 = torch.cat([gs["Wcat"][:hw], gs["Wcat"][hw:]] + [extras[o_] for o_ in order], 1)
             sc_grads = (dW0, None, None, None, gs["b1"], gs["w2"].reshape(1, -1), gs["b2"])
         else:
-            sc_grads = tuple(gs[k_] for k_ in _FusedDGGMlpConvFn.SC_KEYS)
-        for k_ in layer.PARAM_KEYS:
-            g[k_] = g[k_].reshape(P[k_].shape)
-        g = _unpad_grads(g, layer.PARAM_KEYS, ctx.d_orig)
-        return (g.get("x"), None, None, None) + sc_grads + tuple(g[k_] for k_ in layer.PARAM_KEYS)
+            sc_grads = tuple(gs[k_] for k_ in _SC_KEYS)
+        return (g.get("x"), None, None, None) + sc_grads + tuple(g[k_] for k_ in ctx.layer.PARAM_KEYS)
 
 
 class DGG_LearnableK_debug(nn.Module):
@@ -803,7 +790,7 @@ class DGG_LearnableK_debug(nn.Module):
         if chunked and _capturing():
             # nothing can be read back under capture: the layout of the last eager forward on this module, with some slack, becomes a
             # FIXED capacity whose overflow flags check_ell_bound() reads; no wide row then: the list, with its enforced bound
-            last = getattr(layer, "last_layout", None)
+            last = layer.last_layout
             layer.wide_cap = None if last is None or last[0] == N else (last[0] + last[0] // 8 + 64, min(ops.chunk_maxm_for(N), last[1] + max(1, last[1] // 8)))
             if layer.wide_cap is None:
                 layer.wide_rows = "off"
@@ -822,7 +809,7 @@ class DGG_LearnableK_debug(nn.Module):
         and the returned adjacencies"""
         st, N = layer.saved, layer.N
         if noise_mode == ops.NOISE_RANKED_SYM:                # the reference's DEFAULT noise (symmetric_noise=True, dgm.py:1216-1223): the
-            self._note_rsym(getattr(layer, "rsym_last", None), N)     # generator's status words, checked by check_ell_bound as for the modules
+            self._note_rsym(layer.rsym_last, N)     # generator's status words, checked by check_ell_bound as for the modules
             if layer.sym_hash:
                 self._sym_switch()
         if st.get("partp") is None:                           # (shape outside the partitioned backward: the separate modules)

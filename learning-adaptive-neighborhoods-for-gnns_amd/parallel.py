@@ -35,9 +35,11 @@ reduce-scatters the partial [dxp | dH] (the adjoint of that all-gather) and form
 rank's own rows.
 
 `kern` is the kernel namespace (dgg_amd.ops on the GPU; tests substitute a CPU stand-in built on the oracle so
-that the partition / collective logic is exercised with gloo, world_size 2 and 3, without a GPU).
+that the partition / collective logic is exercised with gloo, world_size 2 and 3, without a GPU).  What the engine may call on it
+beyond the baseline entries is written down in KernelContract.
 """
 import os
+import types
 import weakref
 
 import torch
@@ -101,6 +103,116 @@ def _all_gather_rows(t_local, N, per, group, bufs=None, key=None):
     return _Gather(t_local, N, per, group, False, bufs, key).get()
 
 
+class KernelContract:
+    """What ShardedDGGConv may call on its kernel namespace BEYOND the baseline entries (linear_fwd / linear_bwd, degree_stats,
+    knet_x_fwd / knet_x_bwd, allpairs_topk, edgelist_topk, edgelist_topk_p, edge_mlp_fwd / edge_mlp_bwd, softk_fwd / softk_bwd,
+    normalize_fwd, spmm_fwd / spmm_bwd, act_bwd, norm_bwd_da, edge_bwd), written down once.  Every optional entry answers None --
+    what dgg_amd.ops answers for "does not cover this shape" -- and every optional flag is off, so the engine calls them
+    unconditionally and takes its fallback where it takes the shape fallback.  dgg_amd.ops provides every name with these parameter
+    names (tests/test_kernel_contract.py); a test stand-in inherits from this class and defines the baseline entries only."""
+
+    KNET_MFMA_WIDTHS = ()       # latent widths of the matrix-core k-net (knet_x_fwd_slim / knet_x_bwd_fused)
+    PREMASK = False             # softk_edge_bwd_p / knet_x_bwd_fused can return gradients of the pre-activation (out_act)
+    DA_MAP = False              # conv_bwd_cols_p(want_dA=False): the row kernel reads dA through the partition's slot -> record map
+    EMLP_BWD_PARTP = False      # edge_mlp_bwd takes the payload partition for its neighbour-side sums
+
+    def linear_fwd_multi(self, x, layers):
+        return None
+
+    def linear_bwd_multi(self, x, layers):
+        return None
+
+    def zero_pool(self, device, nfloats):
+        return None
+
+    def knet_x_fwd_slim(self, xk, deg, mu_sd, W1, b1, Wmu, bmu, Wp, bp):
+        return None
+
+    def knet_x_bwd_fused(self, xk, deg, mu_sd, W1, b1, Wmu, bmu, Wp, u, dk, out_act=0):
+        return None
+
+    def edgelist_topk_softk(self, xp, rowptr, col, k, mode, K, t, noise_mode, G, seed, overflow=None, rows=None):
+        return None
+
+    def allpairs_topk_softk(self, xp, k, mode, t, seed, rows=None, lpub=None):
+        return None
+
+    def allpairs_topk_wide(self, xp, k, layout, mode, t, seed, rows=None, ramp=True, noise_mode=None, lpub=None):
+        return None
+
+    def chunk_layout(self, k, maxm=None, ccap=None, ncols=None, sticky=None):
+        return None
+
+    def rowmin_logp_bound(self, xp, t, rows=None):
+        return None
+
+    def ranked_probe(self, xp, k_limit, t, seed, rows=None, stride=1, max_blocks=0):
+        return None
+
+    def ranked_cost_estimate(self, probe, N, rows=None):
+        return None
+
+    # rsym_status is never called by the engine (a diagnostic that synchronises).  It stands for the one capability that is not "call
+    # it, see None": the real namespace's allpairs_topk takes `status=` and reports the ranked symmetric generator's flags through it,
+    # a stand-in's has no such parameter.  One boolean in ShardedDGGConv.__init__: the namespace is not built on this class.
+    def rsym_status(self, ws, N, rows=None):
+        return None
+
+    def partp_build(self, idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None):
+        return None
+
+    def partp_sort(self, part):
+        return None
+
+    def partp_has_map(self, rows):
+        return None
+
+    def part_build(self, idx, w, ncols):
+        return None
+
+    def conv_bwd_cols(self, idx, ahat, H, G, part, rs=None, want_da=False):
+        return None
+
+    def conv_bwd_cols_p(self, idx, H, G, partp, rs, zero_dA=True, dA_ext=None, want_dA=True):
+        return None
+
+    def softk_edge_bwd(self, xp, idx, val, k, dA, rs=None, da=None, row0=0, t=-0.05, perturb=False, mode=0, normalized=False, part=None,
+                       want_dval=False, ahat_rows=None):
+        return None
+
+    def softk_edge_bwd_p(self, xp, idx, val, k, dA, dA_rec, rs, da, row0, t, perturb, mode, normalized, partp, ahat_rows=None, out_act=0,
+                         phase=0, state=None):
+        return None
+
+
+def uvdist_score_bwd(kern, xp, idx, val, k, dA, rs, da, row0, t, perturb, mode, normalized, part=None, ahat_rows=None):
+    """Ramp (+ normalisation, if `normalized`) + u-v-dist score backward on an ELL block with an optional index partition -> dxp, dk.
+    Inside the row kernel of the score backward when the partition is there and the entry covers the shape, else the two calls."""
+    fused = None
+    if part is not None:
+        fused = kern.softk_edge_bwd(xp, idx, val, k, dA, rs, da, row0, t, perturb, mode, normalized, part, ahat_rows=ahat_rows)
+    if fused is not None:
+        return fused[0], fused[1]
+    assert ahat_rows is None
+    dval, dk = kern.softk_bwd(idx, val, k, dA, rs, da, row0, mode, normalized)
+    pk = {} if part is None else {"part": part}
+    return kern.edge_bwd(xp, idx, val, dval, row0, t, perturb, **pk), dk
+
+
+def edge_mlp_score_bwd(kern, sc, xp, AB, idx, eid, val, dval, sdeg, ex, perturb, **kw):
+    """Backward of the edge-MLP scorer from d loss / d score: the MLP's backward on the entries (dgg_edge_mlp_bwd: per-node dAB,
+    parameter sums), then AB's GEMM backward -> dxp (WITHOUT the ex_mode == 2 distance term, whose form -- ELL or CSR -- is the
+    caller's), dex (None unless ex_mode == 2), {Wcat, wdu, wdv, wex, b1, w2, b2}.  sc: the scorer's terms (ShardedDGGConv.scorer);
+    kw: edge_mlp_bwd's rows / rowptr / partp / w / nrec_max."""
+    dAB, dpar, dex = kern.edge_mlp_bwd(AB, idx, eid, val, dval, sdeg, ex, sc["wdu"], sc["wdv"], sc["wex"], sc["b1"], sc["w2"], sc["b2"],
+                                       sc["act"], perturb, need_dex=sc["ex_mode"] == 2, **kw)
+    dxp, dWcat, _ = kern.linear_bwd(xp, sc["Wcat"], AB, dAB, 0, 0, True, False)
+    hw = sc["Wcat"].shape[0] // 2
+    pick = lambda t_, a: None if t_ is None else dpar[a * hw:(a + 1) * hw]  # noqa: E731
+    return dxp, dex, dict(Wcat=dWcat, wdu=pick(sc["wdu"], 0), wdv=pick(sc["wdv"], 1), wex=pick(sc["wex"], 2), b1=dpar[3 * hw:4 * hw],
+                          w2=dpar[4 * hw:5 * hw], b2=dpar[5 * hw:5 * hw + 1])
+
+
 class ShardedDGGConv:
     """One DGG (all-pairs or edge-list candidates; u-v-dist or, on edge lists, an edge-MLP scorer / x / k_times_edge_prob) + normalise +
     GCNConv layer, forward and backward, on a row shard.  Parameters are a dict with the reference's names (dgm.py:1097-1143, model.py:583).
@@ -111,6 +223,11 @@ class ShardedDGGConv:
 
     def __init__(self, kern, N, group=None, K=64, t=-0.05, noise_mode=2, seed=(1234, 0), mode=0, algo=0, x_grad=False, x_full=None,
                  hybrid=False, cand=None):
+        if not isinstance(kern, (KernelContract, types.ModuleType)):
+            # an OBJECT that does not inherit the contract (a stand-in written before there was one; the earlier version of this
+            # project's host tests has such a class): the contract becomes a base of its class, behind its own names.  A module --
+            # dgg_amd.ops -- is never touched: a contract name it lacks raises AttributeError where it is called.
+            kern.__class__ = type(type(kern).__name__, (type(kern), KernelContract), {})
         self.kern, self.N, self.group = kern, N, group
         # cand = (rowptr int64 [N+1], col int32 [E]): the candidates of row i are the stored entries of in_adj (edge-list mode, the
         # live class's semantics dgm.py:1613-1614) instead of all N columns; every candidate is scored (per-pair hash noise), the rest
@@ -137,7 +254,7 @@ class ShardedDGGConv:
         # 1.244-1.246 (0), 1.252-1.255 (3): the sort beside the gather-bound aggregation LOSES 8 us (it stretched from 36 to 168 us and
         # took the aggregation with it), the MFMA-bound k-net backward beside the gather-bound column kernel wins 11
         ov = os.environ.get("DGG_OVERLAP", "2")
-        self.overlap = ov != "0" and hasattr(kern, "partp_sort")
+        self.overlap = ov != "0"
         self.overlap_sort, self.overlap_knet = ov in ("1", "3"), ov in ("1", "2")
         self._side = None
         self.K, self.t, self.noise_mode, self.seed, self.mode, self.algo, self.x_grad = K, t, noise_mode, seed, mode, algo, x_grad
@@ -173,11 +290,21 @@ class ShardedDGGConv:
         self.force_chunked = False
         self.tight_bound = "off"                             # ranked search: row-minimum distance bound in its stop tests (_row_bound)
         self._tight_on, self._tight_n, self.tight_probe = False, 0, None
+        # allpairs_topk takes `status=` (KernelContract.rsym_status): true of dgg_amd.ops, not of a stand-in built on the contract
+        self._rsym_status = not isinstance(kern, KernelContract)
+        self.overflow = None                                 # int32[1] device flag the caller owns: the K-wide edge list dropped a weighted rank
+        self.want_backward = True                            # False (the autograd node, no backward can follow): the partition is not sorted
+        self.rsym_err = None                                 # ranked symmetric generator out of workspace: device flags since check_generator()
+        self.rsym_last = None                                # ... and all status words of the last forward that ran it
+        self.last_layout = None                              # (chunks, widest row) of the last chunk layout that was read back
+        self.saved = None                                    # the last forward's state (keys: the stages' docstrings); read by backward()
+        self._fwd_gen = 0                                    # forwards so far: saved["gen"] ties a backward to its forward
+        self._stats_ref, self._stats_ver, self._stats = None, None, None     # degree statistics of the last prior-degree tensor (_learned_degree)
 
     def check_generator(self):
         """raises if the ranked symmetric noise generator (noise_mode 5) could not settle every row inside its workspace in any
         forward since the last call (one synchronisation; the rows concerned came back empty)"""
-        err, self.rsym_err = getattr(self, "rsym_err", None), None
+        err, self.rsym_err = self.rsym_err, None
         if err is not None and bool(err.any()):
             raise RuntimeError("ShardedDGGConv: the ranked symmetric noise generator ran out of workspace for its dense tier; "
                                "use noise_mode 3 (per-pair hash) for this data")
@@ -205,7 +332,7 @@ class ShardedDGGConv:
     def _chunk_layout(self, k):
         """-> ops.ChunkLayout for this forward's learned degrees, or None: every row fits the 64-rank list (or wide_rows is off)"""
         kern = self.kern
-        if self.wide_rows == "off" or not hasattr(kern, "chunk_layout") or self.noise_mode not in self.WIDE_NOISE or self.cand is not None or self.K != 64:
+        if self.wide_rows == "off" or self.noise_mode not in self.WIDE_NOISE or self.cand is not None or self.K != 64:
             return None
         if self.wide_cap is not None:
             if self.wide_sticky is None or self.wide_sticky.device != k.device:
@@ -213,11 +340,14 @@ class ShardedDGGConv:
                 #  would be replayed, i.e. the word would only cover one replay)
                 self.wide_sticky = torch.zeros((1,), device=k.device, dtype=torch.int32)
             lay = kern.chunk_layout(k, maxm=int(self.wide_cap[1]), ccap=int(self.wide_cap[0]), sticky=self.wide_sticky)
-            self.wide_meta = lay.meta
+            if lay is not None:
+                self.wide_meta = lay.meta
             return lay
         assert not (k.is_cuda and torch.cuda.is_current_stream_capturing()), \
             "ShardedDGGConv: chunked rows inside a hipGraph capture need a fixed capacity (wide_cap = (chunks, lists))"
         lay = kern.chunk_layout(k, ncols=self.N)
+        if lay is None:
+            return None
         self.last_layout = (lay.chunks, lay.maxm)
         chunked = lay.wide or self.force_chunked
         if self.coll and self.noise_mode == 5:
@@ -241,7 +371,7 @@ class ShardedDGGConv:
         at N = 100 000) the same stop test uses G + log p_max(i).  tight_bound: "off" | "on" | "auto" = on when a pilot walk (~1000
         sampled rows, 64-block budget, every 16th forward and never inside a capture) puts the search's cost above 2.5 x the sweep's."""
         kern = self.kern
-        if self.tight_bound == "off" or not hasattr(kern, "rowmin_logp_bound") or xp.shape[1] not in (16, 32, 64, 128) or self.t >= 0:
+        if self.tight_bound == "off" or xp.shape[1] not in (16, 32, 64, 128) or self.t >= 0:
             return None
         if self.tight_bound == "auto":
             capturing = xp.is_cuda and torch.cuda.is_current_stream_capturing()
@@ -251,6 +381,8 @@ class ShardedDGGConv:
                     sd = seed.cpu()
                     seed = (int(sd[0]) & 0xFFFFFFFF, int(sd[1]) & 0xFFFFFFFF)
                 pr = kern.ranked_probe(xp, k, self.t, seed, rows=(self.r0, self.r1), stride=max(1, (self.r1 - self.r0) // 1024), max_blocks=64)
+                if pr is None:
+                    return None
                 est = kern.ranked_cost_estimate(pr, self.N, rows=self.r1 - self.r0)
                 sweep_us = 1400.0 * (self.N / 1e5) * ((self.r1 - self.r0) / 1e5) * (xp.shape[1] + 16) / 80.0
                 self._tight_on = est > 2.5 * sweep_us and self.N >= 8192
@@ -284,29 +416,28 @@ class ShardedDGGConv:
         self.r0, self.r1, self.per = shard_bounds(self.N, world, rank)
 
     # ------------------------------------------------------------------------------------------------------------------
+    def _linear_fwd_multi(self, x, layers):
+        """several layers on one input: one GEMM that reads x once when the kernel namespace offers it (ops.linear_fwd_multi; the
+        multi entry reaches the persistent register kernel for large N), one plain call per layer otherwise"""
+        got = self.kern.linear_fwd_multi(x, layers)
+        if got is None:
+            got = [self.kern.linear_fwd(x, W, b, act, lay) for W, b, act, lay in layers]
+        return got
+
     def _project(self, x_local, P):
-        """-> xp (rows of `Xall`), H (rows of `Xall`; hybrid: the rank's OWN rows), xk (own rows).  One GEMM that reads X once when
-        the kernel namespace offers it (ops.linear_fwd_multi), three plain calls otherwise."""
-        kern = self.kern
+        """-> xp (rows of `Xall`), H (rows of `Xall`; hybrid: the rank's OWN rows), xk (own rows)"""
         repl = self.x_full is not None
         Xall = self.x_full if repl else x_local
-        single = not repl or (self.world == 1 and self.emulate is None)      # the own rows are all the rows that are projected
-        if self.hybrid and not single:
-            if hasattr(kern, "linear_fwd_multi"):            # (the multi entry reaches the persistent register kernel for large N)
-                (xp,) = kern.linear_fwd_multi(Xall, [(P["We"], P["be"], 1, 0)])
-                xk, H = kern.linear_fwd_multi(x_local, [(P["Wk"], P["bk"], 1, 0), (P["Wc"], None, 0, 1)])
-                return xp, H, xk
-            xp = kern.linear_fwd(Xall, P["We"], P["be"], 1, 0)
-            return xp, kern.linear_fwd(x_local, P["Wc"], None, 0, 1), kern.linear_fwd(x_local, P["Wk"], P["bk"], 1, 0)
-        if hasattr(kern, "linear_fwd_multi"):
-            if single:
-                xp, xk, H = kern.linear_fwd_multi(Xall, [(P["We"], P["be"], 1, 0), (P["Wk"], P["bk"], 1, 0), (P["Wc"], None, 0, 1)])
-                return xp, H, xk
-            xp, H = kern.linear_fwd_multi(Xall, [(P["We"], P["be"], 1, 0), (P["Wc"], None, 0, 1)])
-            return xp, H, kern.linear_fwd(x_local, P["Wk"], P["bk"], 1, 0)
-        xp = kern.linear_fwd(Xall, P["We"], P["be"], 1, 0)
-        H = kern.linear_fwd(Xall, P["Wc"], None, 0, 1)
-        return xp, H, kern.linear_fwd(x_local, P["Wk"], P["bk"], 1, 0)
+        le, lk, lc = (P["We"], P["be"], 1, 0), (P["Wk"], P["bk"], 1, 0), (P["Wc"], None, 0, 1)
+        if not repl or (self.world == 1 and self.emulate is None):           # the own rows are all the rows that are projected
+            xp, xk, H = self._linear_fwd_multi(Xall, [le, lk, lc])
+        elif self.hybrid:
+            (xp,) = self._linear_fwd_multi(Xall, [le])
+            xk, H = self._linear_fwd_multi(x_local, [lk, lc])
+        else:
+            xp, H = self._linear_fwd_multi(Xall, [le, lc])
+            xk = self.kern.linear_fwd(x_local, *lk)
+        return xp, H, xk
 
     def _side_stream(self):
         if self._side is None:
@@ -320,41 +451,101 @@ class ShardedDGGConv:
     def forward(self, x_local, deg_full, P):
         """One forward per backward: `saved` holds views of the persistent collective buffers (the gathered xp / H / row sums),
         which the next forward overwrites."""
-        kern = self.kern
         s = {}
-        self._fwd_gen = getattr(self, "_fwd_gen", 0) + 1
-        repl = self.x_full is not None
+        self._fwd_gen += 1
         xp, H, xk = self._project(x_local, P)
-        s["xp_loc"], s["H_loc"] = xp, H
-        hyb = self._hyb()
-        if self.coll and not repl:                  # xp first (the top-k waits for it), H streams in behind it
-            g_xp = _Gather(xp, self.N, self.per, self.group, True, self.bufs, "xp")
-            g_H = _Gather(H, self.N, self.per, self.group, True, self.bufs, "H")
-        elif hyb and self.coll:                     # H of the own rows only: gathered behind the k-net, the search and the partition
-            g_H = _Gather(H, self.N, self.per, self.group, True, self.bufs, "H")
-        s["xk"] = xk
+        s["xp_loc"], s["H_loc"], s["xk"] = xp, H, xk
+        g_xp, g_H = self._start_gathers(xp, H)
+        self._learned_degree(s, deg_full, P)
+        s["xp"] = xp if g_xp is None else g_xp.get()
+        s["idx"], s["val"], s["w"], rs_local = self._search(s, deg_full)
+        s["rs"] = self._gather_row_sums(rs_local)
+        self._partition(s, rs_local)
+        s["H"] = self._gathered_H(H, g_H)
+        lkw = {} if s["layout"] is None else {"layout": s["layout"]}
+        s["Z"] = self.kern.spmm_fwd(s["idx"], s["ahat"], s["H"], 2, **lkw)    # relu(A (x Wc))
+        s["gen"] = self._fwd_gen
+        self.saved = s
+        return s["Z"]
+
+    def _start_gathers(self, xp, H):
+        """-> (gather of xp or None, gather of H or None), both running"""
+        if self.coll and self.x_full is None:       # xp first (the top-k waits for it), H streams in behind it
+            return (_Gather(xp, self.N, self.per, self.group, True, self.bufs, "xp"),
+                    _Gather(H, self.N, self.per, self.group, True, self.bufs, "H"))
+        if self._hyb() and self.coll:               # H of the own rows only: gathered behind the k-net, the search and the partition
+            return None, _Gather(H, self.N, self.per, self.group, True, self.bufs, "H")
+        return None, None
+
+    def _learned_degree(self, s, deg_full, P):
+        """prior-degree statistics (cached on the degree tensor) + k-net.  Reads s: xk.  Writes s: mu_sd, deg_local, k, u and z, feat
+        (None on the matrix-core k-net, whose backward re-runs layer 1)."""
+        kern, xk = self.kern, s["xk"]
         # mean / std of the prior degrees (dgm.py:1569-1570): an INPUT statistic -- recomputed only when the degree tensor changes
         # (keyed on the tensor OBJECT and its version counter, not on its address: a new tensor is always re-read)
-        ref = getattr(self, "_stats_ref", None)
+        ref = self._stats_ref
         if ref is None or ref() is not deg_full or self._stats_ver != deg_full._version:
             self._stats_ref, self._stats_ver, self._stats = weakref.ref(deg_full), deg_full._version, kern.degree_stats(deg_full)
         s["mu_sd"] = mu_sd = self._stats
-        deg_local = deg_full[self.r0:self.r1].contiguous()
-        s["deg_local"] = deg_local
-        if hasattr(kern, "knet_x_bwd_fused") and xk.shape[1] in getattr(kern, "KNET_MFMA_WIDTHS", ()):
+        s["deg_local"] = deg_local = deg_full[self.r0:self.r1].contiguous()
+        if xk.shape[1] in kern.KNET_MFMA_WIDTHS:
             # k-net on the matrix cores: the forward saves only u; the backward re-runs layer 1 from xk and forms every gradient in one pass
             s["k"], s["u"] = kern.knet_x_fwd_slim(xk, deg_local, mu_sd, P["W1"], P["b1"], P["Wmu"], P["bmu"], P["Wp"].reshape(-1), P["bp"])
             s["z"] = s["feat"] = None
         else:
             s["k"], s["z"], s["u"], s["feat"] = kern.knet_x_fwd(xk, deg_local, mu_sd, P["W1"], P["b1"], P["Wmu"], P["bmu"],
                                                               P["Wp"].reshape(-1), P["bp"])
-        s["xp"] = xp = g_xp.get() if (self.coll and not repl) else xp
+
+    def _search(self, s, deg_full):
+        """scores + perturbation + top-K + ramp of the rank's rows -> idx, val, w, rs_local.  Reads s: xp (all N rows), k.  Writes s:
+        layout (the chunk layout of rows wider than 64 ranks, or None) and, on edge lists, ncand, with a scorer also AB, sdeg, ex, eid."""
+        kern, xp, k = self.kern, s["xp"], s["k"]
+        s["layout"] = None
         if self.cand is not None:
-            # a row shard: its rows' rebased CSR slice and the row-range entries (rows=); the whole graph: exactly the one-rank calls
-            rowptr, col, (e0, e1) = self._cand_rows()
-            rk = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
-            s["ncand"] = int(col.numel())
-        if self.cand is not None and self.scorer is not None:
+            return self._search_edge_list(s, deg_full)
+        if self.noise_mode == 4 and self.K == 64 and xp.shape[1] in (8, 16, 32, 64, 128):
+            # ranked noise: the ramp is applied inside the search kernel, while the settled list is still in registers
+            s["layout"] = lay = self._chunk_layout(k) if xp.shape[1] in (16, 32, 64, 128) else None
+            lkw_ = {}
+            lp = self._row_bound(xp, k)             # upper bounds of log p over a row's other nodes, when the walk is deep enough to pay for them
+            if lp is not None:
+                lkw_["lpub"] = lp
+            if lay is not None:                     # rows wider than 64 ranks: ceil(k_i + 8.5) + 1 ranks of every row, in chunks of 64
+                got = kern.allpairs_topk_wide(xp, k, lay, self.mode, self.t, self.seed, rows=(self.r0, self.r1), **lkw_)
+            else:
+                got = kern.allpairs_topk_softk(xp, k, self.mode, self.t, self.seed, rows=(self.r0, self.r1), **lkw_)
+            if got is not None:
+                return got
+        # the generators without a row-wise early-stopping search (unperturbed scores, per-pair hash noise, the ranked symmetric
+        # generator).  Rows wider than 64 ranks: chunked rows through the threshold-buffer evaluator (any width; the reference's
+        # defaults symmetric_noise=True / perturb_edge_prob=False train into this regime like every other configuration)
+        s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)) else None
+        if lay is not None:
+            return kern.allpairs_topk_wide(xp, k, lay, self.mode, self.t, self.seed, rows=(self.r0, self.r1),
+                                           noise_mode=self.WIDE_NOISE[self.noise_mode])
+        nm = 3 if (self.noise_mode == 5 and self.sym_hash) else self.noise_mode
+        # sym_fallback: a forward the ranked symmetric generator cannot settle (its dense tier overflows: data-dependent)
+        # is redone under the symmetric per-pair hash, and the layer stays with it (one flag read back per forward; not
+        # inside a capture, not across ranks -- every rank would have to take the same decision)
+        # (st None under noise_mode 5: a stand-in kernel namespace without the status plumbing)
+        st = {"sym_fallback": self.sym_fallback and self.world == 1} if (nm == 5 and self._rsym_status) else None
+        kw = {} if st is None else {"status": st}
+        idx, val = kern.allpairs_topk(xp, self.K, self.t, nm, None, self.seed, rows=(self.r0, self.r1), algo=self.algo, k_limit=k, **kw)
+        if st and st.get("rsym_fell_back"):
+            self.sym_hash = True
+        if st and st.get("rsym_err") is not None:      # ranked symmetric generator out of workspace: device flag, read by check_generator()
+            self.rsym_err = st["rsym_err"] if self.rsym_err is None else (self.rsym_err | st["rsym_err"])
+            self.rsym_last = st                     # (all three status words of this forward: the module mirror keeps its own tally)
+        return (idx, val) + tuple(kern.softk_fwd(idx, val, k, self.mode))
+
+    def _search_edge_list(self, s, deg_full):
+        """_search on edge-list candidates (cand), u-v-dist or the edge-MLP scorer"""
+        kern, xp, k = self.kern, s["xp"], s["k"]
+        # a row shard: its rows' rebased CSR slice and the row-range entries (rows=); the whole graph: exactly the one-rank calls
+        rowptr, col, (e0, e1) = self._cand_rows()
+        rk = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
+        s["ncand"] = int(col.numel())
+        if self.scorer is not None:
             # edge-MLP scorer: first layer split into per-node products AB = xp [Wa | Wb]^T (MFMA GEMM, all N nodes) + per-edge terms
             sc = self.scorer
             erow, ex_in = sc["erow"], sc["ex_in"]
@@ -364,75 +555,43 @@ class ShardedDGGConv:
             s["sdeg"] = sdeg = deg_full if sc["wdu"] is not None else None
             p_edge, s["ex"] = kern.edge_mlp_fwd(AB, xp, erow, col, sdeg, ex_in, sc["ex_mode"], sc["t_ex"], sc["wdu"], sc["wdv"],
                                                 sc["wex"], sc["b1"], sc["w2"], sc["b2"], sc["act"])
-            s["idx"], s["val"], s["eid"] = kern.edgelist_topk_p(p_edge, self.N, rowptr, col, self.K, self.noise_mode, None, self.seed, **rk)
-            s["w"], rs_local = kern.softk_fwd(s["idx"], s["val"], s["k"], self.mode)
-        elif self.cand is not None:
-            # (self.overflow: optional int32[1] device flag the caller owns -- set when the K-wide list drops a weighted rank)
-            got = kern.edgelist_topk_softk(xp, rowptr, col, s["k"], self.mode, self.K, self.t, self.noise_mode, None, self.seed,
-                                           overflow=getattr(self, "overflow", None), **rk) if hasattr(kern, "edgelist_topk_softk") else None
-            if got is not None:                     # search + ramp in one launch
-                s["idx"], s["val"], s["w"], rs_local = got
-            else:
-                s["idx"], s["val"] = kern.edgelist_topk(xp, rowptr, col, self.K, self.t, self.noise_mode, None, self.seed, **rk)
-                s["w"], rs_local = kern.softk_fwd(s["idx"], s["val"], s["k"], self.mode)
-        elif self.noise_mode == 4 and self.K == 64 and hasattr(kern, "allpairs_topk_softk") and xp.shape[1] in (8, 16, 32, 64, 128):
-            # ranked noise: the ramp is applied inside the search kernel, while the settled list is still in registers
-            s["layout"] = lay = self._chunk_layout(s["k"]) if xp.shape[1] in (16, 32, 64, 128) else None
-            lkw_ = {}
-            lp = self._row_bound(xp, s["k"])        # upper bounds of log p over a row's other nodes, when the walk is deep enough to pay for them
-            if lp is not None:
-                lkw_["lpub"] = lp
-            if lay is not None:                     # rows wider than 64 ranks: ceil(k_i + 8.5) + 1 ranks of every row, in chunks of 64
-                s["idx"], s["val"], s["w"], rs_local = kern.allpairs_topk_wide(xp, s["k"], lay, self.mode, self.t, self.seed, rows=(self.r0, self.r1), **lkw_)
-            else:
-                s["idx"], s["val"], s["w"], rs_local = kern.allpairs_topk_softk(xp, s["k"], self.mode, self.t, self.seed, rows=(self.r0, self.r1), **lkw_)
-        else:
-            # the generators without a row-wise early-stopping search (unperturbed scores, per-pair hash noise, the ranked symmetric
-            # generator).  Rows wider than 64 ranks: chunked rows through the threshold-buffer evaluator (any width; the reference's
-            # defaults symmetric_noise=True / perturb_edge_prob=False train into this regime like every other configuration)
-            lay = self._chunk_layout(s["k"]) if (xp.shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)) else None
-            s["layout"] = lay
-            if lay is not None:
-                s["idx"], s["val"], s["w"], rs_local = kern.allpairs_topk_wide(xp, s["k"], lay, self.mode, self.t, self.seed, rows=(self.r0, self.r1),
-                                                                             noise_mode=self.WIDE_NOISE[self.noise_mode])
-            else:
-                nm = 3 if (self.noise_mode == 5 and self.sym_hash) else self.noise_mode
-                if nm == 5 and not hasattr(kern, "rsym_status"):      # (a stand-in kernel namespace without the status plumbing)
-                    st = None
-                else:
-                    # sym_fallback: a forward the ranked symmetric generator cannot settle (its dense tier overflows: data-dependent)
-                    # is redone under the symmetric per-pair hash, and the layer stays with it (one flag read back per forward; not
-                    # inside a capture, not across ranks -- every rank would have to take the same decision)
-                    st = {"sym_fallback": self.sym_fallback and self.world == 1} if nm == 5 else None
-                kw = {} if st is None else {"status": st}
-                s["idx"], s["val"] = kern.allpairs_topk(xp, self.K, self.t, nm, None, self.seed,
-                                                        rows=(self.r0, self.r1), algo=self.algo, k_limit=s["k"], **kw)
-                if st and st.get("rsym_fell_back"):
-                    self.sym_hash = True
-                if st and st.get("rsym_err") is not None:      # ranked symmetric generator out of workspace: device flag, read by check_generator()
-                    self.rsym_err = st["rsym_err"] if getattr(self, "rsym_err", None) is None else (self.rsym_err | st["rsym_err"])
-                    self.rsym_last = st                 # (all three status words of this forward: the module mirror keeps its own tally)
-                s["w"], rs_local = kern.softk_fwd(s["idx"], s["val"], s["k"], self.mode)
-        s["rs"] = rs = _all_gather_rows(rs_local, self.N, self.per, self.group, self.bufs, "rs") if self.coll else rs_local
+            idx, val, s["eid"] = kern.edgelist_topk_p(p_edge, self.N, rowptr, col, self.K, self.noise_mode, None, self.seed, **rk)
+            return (idx, val) + tuple(kern.softk_fwd(idx, val, k, self.mode))
+        got = kern.edgelist_topk_softk(xp, rowptr, col, k, self.mode, self.K, self.t, self.noise_mode, None, self.seed,
+                                       overflow=self.overflow, **rk)
+        if got is not None:                         # search + ramp in one launch
+            return got
+        idx, val = kern.edgelist_topk(xp, rowptr, col, self.K, self.t, self.noise_mode, None, self.seed, **rk)
+        return (idx, val) + tuple(kern.softk_fwd(idx, val, k, self.mode))
+
+    def _gather_row_sums(self, rs_local):
+        """-> the row sums of all N nodes (emulation: the other ranks' faked by tiling the own ones)"""
         if self.emulate is not None:
-            s["rs"] = rs = rs_local.repeat(self.world)[:self.N].contiguous()
-        # destination-bucket partition of the active entries: the backward's column-side terms run on it (no atomics)
-        # (payload form -- records carry w rs_i^-1/2 and the score, no slot map, normalize_adj fused into its fill pass -- when the
-        # namespace offers it and covers the shape)
-        use_p = hasattr(kern, "partp_build") and xp.shape[1] in (16, 32, 64, 128) and H.shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)
+            return rs_local.repeat(self.world)[:self.N].contiguous()
+        return _all_gather_rows(rs_local, self.N, self.per, self.group, self.bufs, "rs") if self.coll else rs_local
+
+    def _partition(self, s, rs_local):
+        """destination-bucket partition of the active entries: the backward's column-side terms run on it (no atomics).  Reads s: idx,
+        w, val, rs, layout, xp, H_loc.  Writes s: partp (payload form -- records carry w rs_i^-1/2 and the score, no slot map,
+        normalize_adj fused into its fill pass -- when the namespace offers it and covers the shape), else part (index form), ahat,
+        partp_sorted (False: want_backward was off and the sort was not launched), side_join (the sort runs on the side stream)."""
+        kern, rs, lay = self.kern, s["rs"], s["layout"]
+        use_p = s["xp"].shape[1] in (16, 32, 64, 128) and s["H_loc"].shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)
         ov = use_p and self.overlap and self.overlap_sort and s["idx"].is_cuda
         # want_backward = False (set by the autograd node under torch.no_grad() / frozen parameters): the per-bucket sort of the
         # partition -- read by the backward's column kernels only -- is not launched at all (ADVICE round 4: an eval forward used to
         # leave it running on the side stream with nothing ever joining it)
-        nobwd = use_p and not getattr(self, "want_backward", True)
-        lay = s.get("layout")
+        nobwd = use_p and not self.want_backward
         lkw = {} if lay is None else {"layout": lay}
+        got = None
+        if use_p and (ov or nobwd):
+            got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, phase=1, **lkw)
+        elif use_p:
+            got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, **lkw)
         assert lay is None or use_p, "chunked rows run on the payload partition (latent / conv widths 16, 32, 64, 128; soft modes)"
-        got = (kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, phase=1, **lkw) if (ov or nobwd) else
-               kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, **lkw)) if use_p else None
         s["partp"], s["ahat"] = got if got is not None else (None, None)
         s["side_join"] = False
-        s["partp_sorted"] = not nobwd
+        s["partp_sorted"] = not (nobwd and got is not None)
         if nobwd and got is not None:
             s["partp"].args = None                  # (phase 1 only: ahat is complete, the records stay in bucket order, unread)
         elif ov and got is not None:                # the sort runs beside the aggregation; the backward joins before its first column kernel
@@ -443,44 +602,45 @@ class ShardedDGGConv:
             if not torch.cuda.is_current_stream_capturing():
                 s["partp"].ws.record_stream(side)
             s["side_join"] = True
-        s["part"] = kern.part_build(s["idx"], s["w"], self.N) if (s["partp"] is None and hasattr(kern, "part_build")) else None
+        s["part"] = kern.part_build(s["idx"], s["w"], self.N) if s["partp"] is None else None
         if s["ahat"] is None:
             s["ahat"] = kern.normalize_fwd(s["idx"], s["w"], rs, self.r0)
-        if self.coll and (not repl or hyb):
-            H = g_H.get()
-        elif hyb:                                   # emulation: the other ranks' rows of H are stale filler in a persistent buffer
-            Hf = _Gather._buf(self.bufs, ("H", "emu"), (self.N, H.shape[1]), H)
-            if not self.bufs.get(("H", "emu_init")):
-                Hf.copy_(H.repeat((self.N + H.shape[0] - 1) // H.shape[0], 1)[:self.N])
-                self.bufs[("H", "emu_init")] = True
-            Hf[self.r0:self.r1].copy_(H)
-            H = Hf
-        s["H"] = H
-        s["Z"] = kern.spmm_fwd(s["idx"], s["ahat"], H, 2, **lkw)    # relu(A (x Wc))
-        s["gen"] = self._fwd_gen
-        self.saved = s
-        return s["Z"]
+
+    def _gathered_H(self, H, g_H):
+        """-> H of all N nodes: the finished gather, the projection itself, or under emulation the own rows in stale filler"""
+        if g_H is not None:
+            return g_H.get()
+        if not self._hyb():
+            return H
+        Hf = _Gather._buf(self.bufs, ("H", "emu"), (self.N, H.shape[1]), H)     # (the other ranks' rows: a persistent buffer)
+        if not self.bufs.get(("H", "emu_init")):
+            Hf.copy_(H.repeat((self.N + H.shape[0] - 1) // H.shape[0], 1)[:self.N])
+            self.bufs[("H", "emu_init")] = True
+        Hf[self.r0:self.r1].copy_(H)
+        return Hf
 
     def backward(self, dZ, x_local, P, dA_ext=None):
         """-> dict of parameter gradients (summed over ranks) and, if x_grad, 'x' = d loss / d x_local.
         dA_ext [rows,K] (optional): cotangent of the NORMALISED adjacency (saved["ahat"]) from consumers other than this layer's own
         aggregation (GCN_DGG's second layer reads the same adjacency); added to the aggregation's own before the score backward."""
         kern, s = self.kern, self.saved
-        assert s.get("gen") == getattr(self, "_fwd_gen", None), "ShardedDGGConv: backward() must follow the forward() it differentiates " \
+        assert s is not None and s["gen"] == self._fwd_gen, "ShardedDGGConv: backward() must follow the forward() it differentiates " \
             "(a second forward has overwritten the gathered buffers)"
-        assert s.get("partp_sorted", True), "ShardedDGGConv: this forward ran with want_backward = False (its partition was not sorted)"
-        if hasattr(kern, "zero_pool"):                   # every zero-initialised accumulator of the backward from ONE filled buffer
-            ncols, h, F = s["xp"].shape[0], s["xp"].shape[1], s["H"].shape[1]
-            rows = s["idx"].shape[0]
-            # (payload path: dH / da / dxp / dA are written by their owner wavefronts, only the weight gradients are accumulated into)
-            need = 3 * sum(int(v.numel()) for v in P.values()) + 65536
-            if s.get("partp") is None:
-                need += rows * self.K + ncols * (h + F + 2)
-            if self.scorer is not None:                  # row-major dA (zero outside the partition), dAB + parameter sums, dWcat, dxp
-                need += rows * self.K + ncols * (2 * self.scorer["Wcat"].shape[0] + h) + 4 * int(self.scorer["Wcat"].numel()) + 4096
-            with kern.zero_pool(s["xp"].device, need):
-                return self._backward(dZ, x_local, P, dA_ext)
-        return self._backward(dZ, x_local, P, dA_ext)
+        assert s["partp_sorted"], "ShardedDGGConv: this forward ran with want_backward = False (its partition was not sorted)"
+        # every zero-initialised accumulator of the backward from ONE filled buffer, where the namespace has such a pool
+        ncols, h, F = s["xp"].shape[0], s["xp"].shape[1], s["H"].shape[1]
+        rows = s["idx"].shape[0]
+        # (payload path: dH / da / dxp / dA are written by their owner wavefronts, only the weight gradients are accumulated into)
+        need = 3 * sum(int(v.numel()) for v in P.values()) + 65536
+        if s["partp"] is None:
+            need += rows * self.K + ncols * (h + F + 2)
+        if self.scorer is not None:                  # row-major dA (zero outside the partition), dAB + parameter sums, dWcat, dxp
+            need += rows * self.K + ncols * (2 * self.scorer["Wcat"].shape[0] + h) + 4 * int(self.scorer["Wcat"].numel()) + 4096
+        pool = kern.zero_pool(s["xp"].device, need)
+        if pool is None:
+            return self._backward(dZ, x_local, P, dA_ext)
+        with pool:
+            return self._backward(dZ, x_local, P, dA_ext)
 
     def _reduce_scatter_rows(self, t, key, async_op=False):
         """[N, c] partial sums on every rank -> the rank's own rows [r1-r0, c], summed over ranks.  async_op: returns a callable
@@ -505,14 +665,35 @@ class ShardedDGGConv:
     def _backward(self, dZ, x_local, P, dA_ext=None):
         kern, s = self.kern, self.saved
         g = {}
-        repl = self.x_full is not None
-        part = s.get("part")
         G = kern.act_bwd(s["Z"], dZ, 2)                  # cotangent of A H
+        dA, dA_rec, dH, da, ahat_rows = self._conv_backward(G, dA_ext)
+        # (da first: both collectives share one RCCL stream and da is an operand of the very next kernel; behind the 25-128 MB
+        #  reduce-scatter it would wait for that transfer -- ADVICE round 4)
+        if self.coll:
+            dist.all_reduce(da, group=self.group)
+        if self._hyb() and self.coll:               # dH [N,F] partial is complete here and needed only by the last kernel of the step
+            dH = self._reduce_scatter_rows(dH, "dH", async_op=True)
+        if self.scorer is not None:
+            dxp, dk = self._scorer_backward(g, dA, da, ahat_rows)
+            return self._weight_grads(g, dxp, dH, dk, x_local, P)
+        if s["partp"] is None:
+            dxp, dk = uvdist_score_bwd(kern, s["xp"], s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.t, self.noise_mode != 0,
+                                       self.mode, True, s["part"], ahat_rows)
+            return self._weight_grads(g, dxp, dH, dk, x_local, P)
+        dxp, dk, pre, kn = self._uvdist_backward_p(dA, dA_rec, da, P)
+        return self._weight_grads(g, dxp, dH, dk, x_local, P, premasked=pre, knet=kn)
+
+    def _conv_backward(self, G, dA_ext):
+        """backward of Z = A H and the neighbour side of the normalisation backward, on whichever partition the forward built
+        -> dA [rows,K] (None: read through the partition's map), dA_rec (payload form only), dH [N,F] partial, da [N], ahat_rows.
+        ahat_rows = saved ahat: `da` holds the neighbour-side sums only and the consumer forms the row side (sqrt(rs_i) sum_r dA_ir
+        ahat_ir) itself; None: `da` is d loss / d (rs^-1/2), both sides.  Reads s: idx, H, rs, w, ahat, partp, part, layout, side_join."""
+        kern, s = self.kern, self.saved
         # one gather of G per edge for SDDMM + transposed SpMM + neighbour side of da; its companion is the fused score backward
         # (which adds the row side of da in registers), so both must cover the shape
-        partp = s.get("partp")
-        if partp is not None:
-            if s.get("side_join"):                  # the partition's sort ran on the side stream
+        partp, part = s["partp"], s["part"]
+        if partp is not None:                       # payload partition
+            if s["side_join"]:                      # the partition's sort ran on the side stream
                 torch.cuda.current_stream().wait_stream(self._side_stream())
                 s["side_join"] = False
             # (dA of the entries outside the partition is masked by the row kernel -- ahat_rows is 0 there -- so it is not zero-filled)
@@ -520,120 +701,91 @@ class ShardedDGGConv:
             # record-ordered copy through the slot -> record map the partition's sort left (Pubmed step 0.359 -> 0.349 ms).  At
             # N = 100 000 (25.6 MB) the 4.1 M four-byte gathers cost the row kernel more (+70 us) than the scattered stores cost the
             # node kernel (-47 us): 1.264 -> 1.285 ms, so large graphs keep the scattered row-major copy.  DGG_DA_MAP=0/1 forces one.
-            use_map = getattr(kern, "DA_MAP", False) and kern.partp_has_map(s["idx"].shape[0]) and self.scorer is None and s.get("layout") is None
+            use_map = kern.DA_MAP and kern.partp_has_map(s["idx"].shape[0]) and self.scorer is None and s["layout"] is None
             kw = {"want_dA": False} if use_map else {}
             if dA_ext is not None:
                 kw["dA_ext"] = dA_ext
             pc = kern.conv_bwd_cols_p(s["idx"], s["H"], G, partp, s["rs"], zero_dA=self.scorer is not None, **kw)
             assert pc is not None
-            dA, dA_rec, dH, da = pc
-            if self.scorer is not None:          # (`da` holds the neighbour-side sums; the row side: sqrt(rs_i) sum_r dA_ir ahat_ir)
-                return self._scorer_backward(g, dA, dH, da, x_local, P, cols_only=True)
-            # (da first: both collectives share one RCCL stream and da is an operand of the very next kernel; behind the 25-128 MB
-            #  reduce-scatter it would wait for that transfer -- ADVICE round 4)
-            if self.coll:
-                dist.all_reduce(da, group=self.group)
-            if self._hyb() and self.coll:           # dH [N,F] partial is complete here and needed only by the last kernel of the step
-                dH = self._reduce_scatter_rows(dH, "dH", async_op=True)
-            # the activation derivative of the two LeakyReLU projections is applied by the kernels that PRODUCE dxp / dxk (they hold
-            # xp_j / xk in registers): the fused weight-gradient product then reads no forward output for the mask (51 MB less)
-            pre = self._premask(x_local)
-            if self.overlap and self.overlap_knet and self.mode == 0 and s["z"] is None and s["idx"].is_cuda:
-                # row kernel -> dk; then the k-net backward on the side stream beside the per-destination kernel on this one
-                dxp, dk, st = kern.softk_edge_bwd_p(s["xp"], s["idx"], s["val"], s["k"], dA, dA_rec, s["rs"], da, self.r0, self.t,
-                                                    self.noise_mode != 0, self.mode, True, partp, ahat_rows=s["ahat"],
-                                                    out_act=1 if pre else 0, phase=1)
-                main, side = torch.cuda.current_stream(), self._side_stream()
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    kn = kern.knet_x_bwd_fused(s["xk"], s["deg_local"], s["mu_sd"], P["W1"], P["b1"], P["Wmu"], P["bmu"],
-                                               P["Wp"].reshape(-1), s["u"], dk, out_act=1 if pre else 0)
-                kern.softk_edge_bwd_p(s["xp"], s["idx"], s["val"], s["k"], dA, dA_rec, s["rs"], da, self.r0, self.t,
-                                      self.noise_mode != 0, self.mode, True, partp, ahat_rows=s["ahat"], out_act=1 if pre else 0,
-                                      phase=2, state=st)
-                main.wait_stream(side)
-                if not torch.cuda.is_current_stream_capturing():
-                    dk.record_stream(side)
-                    for t_ in kn:
-                        t_.record_stream(main)
-                return self._weight_grads(g, dxp, dH, dk, x_local, P, premasked=pre, knet=kn)
-            dxp, dk = kern.softk_edge_bwd_p(s["xp"], s["idx"], s["val"], s["k"], dA, dA_rec, s["rs"], da, self.r0, self.t,
-                                            self.noise_mode != 0, self.mode, True, partp, ahat_rows=s["ahat"], out_act=1 if pre else 0)
-            return self._weight_grads(g, dxp, dH, dk, x_local, P, premasked=pre)
+            return pc + (s["ahat"],)
         cols = None
-        if self.scorer is None and dA_ext is None and part is not None and hasattr(kern, "conv_bwd_cols") and hasattr(kern, "softk_edge_bwd") and \
-                s["xp"].shape[1] in (16, 32, 64, 128) and self.mode in (0, 1):
+        if self.scorer is None and dA_ext is None and part is not None and s["xp"].shape[1] in (16, 32, 64, 128) and self.mode in (0, 1):
             cols = kern.conv_bwd_cols(s["idx"], s["ahat"], s["H"], G, part, s["rs"], True)
-        if cols is not None:
+        if cols is not None:                        # index partition
             dA, dH, da = cols
-            ahat_rows = s["ahat"]
-        else:
-            dA, dH = kern.spmm_bwd(s["idx"], s["ahat"], s["H"], G, True, True)
-            if dA_ext is not None:                       # (the slot-wise total; the masked entries carry no weight either way)
-                dA = dA + torch.where(s["idx"] >= 0, dA_ext, torch.zeros_like(dA_ext))
-            da = kern.norm_bwd_da(s["idx"], s["w"], s["rs"], dA, self.r0, part) if part is not None else \
-                kern.norm_bwd_da(s["idx"], s["w"], s["rs"], dA, self.r0)
-            ahat_rows = None
-        if self.scorer is not None:
-            return self._scorer_backward(g, dA, dH, da, x_local, P)
-        if self.coll:
-            dist.all_reduce(da, group=self.group)
-        if self._hyb() and self.coll:
-            dH = self._reduce_scatter_rows(dH, "dH", async_op=True)
-        fused = None
-        if part is not None and hasattr(kern, "softk_edge_bwd"):
-            fused = kern.softk_edge_bwd(s["xp"], s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.t, self.noise_mode != 0,
-                                        self.mode, True, part, ahat_rows=ahat_rows)
-        if fused is not None:                            # ramp + normalisation backward inside the row kernel of the score backward
-            dxp, dk, _ = fused
-        else:
-            assert ahat_rows is None
-            dval, dk = kern.softk_bwd(s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.mode, True)
-            dxp = kern.edge_bwd(s["xp"], s["idx"], s["val"], dval, self.r0, self.t, self.noise_mode != 0, part) \
-                if part is not None else kern.edge_bwd(s["xp"], s["idx"], s["val"], dval, self.r0, self.t, self.noise_mode != 0)
-        return self._weight_grads(g, dxp, dH, dk, x_local, P)
+            return dA, None, dH, da, s["ahat"]
+        dA, dH = kern.spmm_bwd(s["idx"], s["ahat"], s["H"], G, True, True)      # atomic baseline
+        if dA_ext is not None:                       # (the slot-wise total; the masked entries carry no weight either way)
+            dA = dA + torch.where(s["idx"] >= 0, dA_ext, torch.zeros_like(dA_ext))
+        pk = () if part is None else (part,)
+        return dA, None, dH, kern.norm_bwd_da(s["idx"], s["w"], s["rs"], dA, self.r0, *pk), None
 
-    def _scorer_backward(self, g, dA, dH, da, x_local, P, cols_only=False):
-        """score backward of the edge-MLP scorer: ramp + normalisation backward by rows, the MLP's backward on the selected
-        edges (dgg_edge_mlp_bwd: per-node dAB, parameter sums), AB's GEMM backward into dxp; the k-net and the fused weight gradients
-        as for the distance scorer.  da [N]: d loss / d (rs^-1/2), both sides (dgg_norm_bwd_da), or with cols_only the neighbour-side
-        sums (the row side is then formed inside the row kernel, dgg_softk_bwd_rows)."""
+    def _uvdist_backward_p(self, dA, dA_rec, da, P):
+        """ramp + normalisation + u-v-dist score backward on the payload partition -> dxp, dk, premasked, the k-net's gradients when
+        its backward already ran beside the column kernel (else None).  Reads s: xp, idx, val, k, rs, ahat, partp, xk, deg_local,
+        mu_sd, u, z."""
+        kern, s = self.kern, self.saved
+        # the activation derivative of the two LeakyReLU projections is applied by the kernels that PRODUCE dxp / dxk (they hold
+        # xp_j / xk in registers): the fused weight-gradient product then reads no forward output for the mask (51 MB less)
+        pre = self._premask()
+        args = (s["xp"], s["idx"], s["val"], s["k"], dA, dA_rec, s["rs"], da, self.r0, self.t, self.noise_mode != 0, self.mode, True, s["partp"])
+        kw = dict(ahat_rows=s["ahat"], out_act=1 if pre else 0)
+        if not (self.overlap and self.overlap_knet and self.mode == 0 and s["z"] is None and s["idx"].is_cuda):
+            dxp, dk = kern.softk_edge_bwd_p(*args, **kw)
+            return dxp, dk, pre, None
+        # row kernel -> dk; then the k-net backward on the side stream beside the per-destination kernel on this one
+        dxp, dk, st = kern.softk_edge_bwd_p(*args, **kw, phase=1)
+        main, side = torch.cuda.current_stream(), self._side_stream()
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            kn = kern.knet_x_bwd_fused(s["xk"], s["deg_local"], s["mu_sd"], P["W1"], P["b1"], P["Wmu"], P["bmu"],
+                                       P["Wp"].reshape(-1), s["u"], dk, out_act=1 if pre else 0)
+        kern.softk_edge_bwd_p(*args, **kw, phase=2, state=st)
+        main.wait_stream(side)
+        if not torch.cuda.is_current_stream_capturing():
+            dk.record_stream(side)
+            for t_ in kn:
+                t_.record_stream(main)
+        return dxp, dk, pre, kn
+
+    def _scorer_backward(self, g, dA, da, ahat_rows):
+        """score backward of the edge-MLP scorer: ramp + normalisation backward by rows, then edge_mlp_score_bwd on the selected
+        edges -> dxp, dk; writes g["scorer"].  da [N]: d loss / d (rs^-1/2), both sides (dgg_norm_bwd_da), or with ahat_rows the
+        neighbour-side sums (the row side is then formed inside the row kernel, dgg_softk_bwd_rows).  Reads s: idx, val, k, rs, xp, AB,
+        eid, sdeg, ex and, for the payload form of the MLP's backward, partp, w, ncand."""
         kern, s, sc = self.kern, self.saved, self.scorer
-        if self.coll:                                   # (as in _backward: da summed over the ranks, dH's own rows reduce-scattered behind)
-            dist.all_reduce(da, group=self.group)
-        if self._hyb() and self.coll:
-            dH = self._reduce_scatter_rows(dH, "dH", async_op=True)
-        if cols_only:
-            dval, dk = kern.softk_bwd(s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.mode, True, ahat_rows=s["ahat"])
-        else:
-            dval, dk = kern.softk_bwd(s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.mode, True)
+        akw = {} if ahat_rows is None else {"ahat_rows": ahat_rows}
+        dval, dk = kern.softk_bwd(s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.mode, True, **akw)
         kw = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
-        if s.get("partp") is not None and self.cand is not None and getattr(kern, "EMLP_BWD_PARTP", False):
+        if s["partp"] is not None and self.cand is not None and kern.EMLP_BWD_PARTP:
             kw.update(partp=s["partp"], w=s["w"], nrec_max=s["ncand"])       # (a selected entry is one of the rows' candidate edges)
-        dAB, dpar, dex = kern.edge_mlp_bwd(s["AB"], s["idx"], s["eid"], s["val"], dval, s["sdeg"], s["ex"], sc["wdu"], sc["wdv"], sc["wex"],
-                                           sc["b1"], sc["w2"], sc["b2"], sc["act"], self.noise_mode != 0, need_dex=sc["ex_mode"] == 2, **kw)
-        dxp, dWcat, _ = kern.linear_bwd(s["xp"], sc["Wcat"], s["AB"], dAB, 0, 0, True, False)
+        dxp, dex, g["scorer"] = edge_mlp_score_bwd(kern, sc, s["xp"], s["AB"], s["idx"], s["eid"], s["val"], dval, s["sdeg"], s["ex"],
+                                                   self.noise_mode != 0, **kw)
         if sc["ex_mode"] == 2:                              # exp(t ||xp_u - xp_v||) as an edge feature also depends on the projection
             dxp = dxp + kern.edge_bwd(s["xp"], s["idx"], s["val"], dex, self.r0, sc["t_ex"], False)
-        hw = sc["Wcat"].shape[0] // 2
-        pick = lambda t_, a: None if t_ is None else dpar[a * hw:(a + 1) * hw]  # noqa: E731
-        g["scorer"] = dict(Wcat=dWcat, wdu=pick(sc["wdu"], 0), wdv=pick(sc["wdv"], 1), wex=pick(sc["wex"], 2), b1=dpar[3 * hw:4 * hw],
-                           w2=dpar[4 * hw:5 * hw], b2=dpar[5 * hw:5 * hw + 1])
-        return self._weight_grads(g, dxp, dH, dk, x_local, P, premasked=False)
+        return dxp, dk
 
-    def _premask(self, x_local):
+    def _premask(self):
         """True when the step's weight gradients go through linear_bwd_multi (no input gradient) and the producers of dxp / dxk can
         apply LeakyReLU' themselves (ranked / k_times_edge_prob path on the HIP kernels)"""
-        kern = self.kern
-        return bool(getattr(kern, "PREMASK", False)) and hasattr(kern, "linear_bwd_multi") and not self.x_grad and self.mode == 0 and \
-            self.saved["z"] is None and not (self.coll and self.x_full is None)
+        return bool(self.kern.PREMASK) and not self.x_grad and self.mode == 0 and self.saved["z"] is None and \
+            not (self.coll and self.x_full is None)
+
+    def _linear_bwd_multi(self, X, layers):
+        """weight (and bias) gradients of layers that share the input X -> [(dW, db or None)]: one pass over X (leaky masks applied on
+        the operand load) when the kernel namespace offers it, one linear_bwd per layer otherwise"""
+        got = self.kern.linear_bwd_multi(X, layers)
+        if got is None:
+            got = [self.kern.linear_bwd(X, W, y, dy, act, lay, False, need_db)[1:] for W, y, dy, act, lay, need_db in layers]
+        return got
 
     def _weight_grads(self, g, dxp, dH, dk, x_local, P, premasked=False, knet=None):
+        """k-net backward (unless `knet` already holds it), weight gradients of the three projections, their all-reduce, d loss / dx.
+        Reads s: xp, xp_loc, xk, deg_local, mu_sd, u, z, feat."""
         kern, s = self.kern, self.saved
         repl = self.x_full is not None
         # weight gradients of the two projections.  Replicated features: partial [dxp | dH] of all N nodes against the full X (the
         # weight all-reduce sums the ranks); gathered projections: reduce-scatter the partials, then the rank's own rows only.
-        hyb = self._hyb()
         if self.coll and not repl:
             both = self._reduce_scatter_rows(torch.cat([dxp, dH], 1), "dproj")
             h = dxp.shape[1]
@@ -642,50 +794,37 @@ class ShardedDGGConv:
             dxp_g, dH_g, Xg, xp_g = dxp, dH, (self.x_full if repl else x_local), s["xp"]
         if knet is not None:                         # already run (beside the score backward's column kernel)
             dxk, g["W1"], g["b1"], g["Wmu"], g["bmu"], dWp, g["bp"] = knet
-        elif s["z"] is None and premasked:
-            dxk, g["W1"], g["b1"], g["Wmu"], g["bmu"], dWp, g["bp"] = kern.knet_x_bwd_fused(
-                s["xk"], s["deg_local"], s["mu_sd"], P["W1"], P["b1"], P["Wmu"], P["bmu"], P["Wp"].reshape(-1), s["u"], dk, out_act=1)
         elif s["z"] is None:
+            okw = {"out_act": 1} if premasked else {}
             dxk, g["W1"], g["b1"], g["Wmu"], g["bmu"], dWp, g["bp"] = kern.knet_x_bwd_fused(
-                s["xk"], s["deg_local"], s["mu_sd"], P["W1"], P["b1"], P["Wmu"], P["bmu"], P["Wp"].reshape(-1), s["u"], dk)
+                s["xk"], s["deg_local"], s["mu_sd"], P["W1"], P["b1"], P["Wmu"], P["bmu"], P["Wp"].reshape(-1), s["u"], dk, **okw)
         else:
             dxk, g["W1"], g["b1"], g["Wmu"], g["bmu"], dWp, g["bp"] = kern.knet_x_bwd(
                 s["xk"].shape[1], s["mu_sd"], P["W1"], P["Wmu"], P["bmu"], P["Wp"].reshape(-1), s["z"], s["u"], s["feat"], dk)
         g["Wp"] = dWp.reshape(P["Wp"].shape)
         same_rows = Xg.shape[0] == x_local.shape[0] and (not repl or self.world == 1) and self.emulate is None
-        if hyb:
+        ym, am = (None, 0) if premasked else (True, 1)          # premasked: dxp / dxk already carry LeakyReLU'
+        le = (P["We"], xp_g if ym else None, dxp_g, am, 0, True)
+        lk = (P["Wk"], s["xk"] if ym else None, dxk, am, 0, True)
+        dX1 = dX2 = dX3 = None
+        if self._hyb():
             # hybrid: dWe from the rank's PARTIAL dxp of all N nodes against the full X (summed by the weight all-reduce); dWk and dWc
             # from the rank's own rows -- dH_own = the reduce-scattered sum over ranks (emulation: the rank's own rows of its partial)
             dH_own = dH_g() if callable(dH_g) else dH_g[self.r0:self.r1]
-            ym, am = (None, 0) if premasked else (True, 1)
-            if hasattr(kern, "linear_bwd_multi"):
-                ((g["We"], g["be"]),) = kern.linear_bwd_multi(Xg, [(P["We"], xp_g if ym else None, dxp_g, am, 0, True)])
-                (g["Wk"], g["bk"]), (g["Wc"], _) = kern.linear_bwd_multi(
-                    x_local, [(P["Wk"], s["xk"] if ym else None, dxk, am, 0, True), (P["Wc"], None, dH_own, 0, 1, False)])
-            else:
-                _, g["We"], g["be"] = kern.linear_bwd(Xg, P["We"], xp_g if ym else None, dxp_g, am, 0, False, True)
-                _, g["Wk"], g["bk"] = kern.linear_bwd(x_local, P["Wk"], s["xk"] if ym else None, dxk, am, 0, False, True)
-                _, g["Wc"], _ = kern.linear_bwd(x_local, P["Wc"], None, dH_own, 0, 1, False, False)
+            ((g["We"], g["be"]),) = self._linear_bwd_multi(Xg, [le])
+            (g["Wk"], g["bk"]), (g["Wc"], _) = self._linear_bwd_multi(x_local, [lk, (P["Wc"], None, dH_own, 0, 1, False)])
             # (dWc comes from the ALREADY SUMMED dH of the own rows: in the flat weight all-reduce below every rank's part is its share
             # of the total, so the sum over ranks is the whole gradient -- as for every other weight)
-            dX1 = dX2 = dX3 = None
-        elif hasattr(kern, "linear_bwd_multi") and not self.x_grad and same_rows:
-            # one pass over X for the three weight gradients (leaky masks applied on the operand load)
-            ym, am = (None, 0) if premasked else (True, 1)          # premasked: dxp / dxk already carry LeakyReLU'
-            (g["We"], g["be"]), (g["Wk"], g["bk"]), (g["Wc"], _) = kern.linear_bwd_multi(
-                Xg, [(P["We"], xp_g if ym else None, dxp_g, am, 0, True), (P["Wk"], s["xk"] if ym else None, dxk, am, 0, True),
-                     (P["Wc"], None, dH_g, 0, 1, False)])
-            dX1 = dX2 = dX3 = None
-        elif hasattr(kern, "linear_bwd_multi") and not self.x_grad:
-            ym, am = (None, 0) if premasked else (True, 1)
-            (g["We"], g["be"]), (g["Wc"], _) = kern.linear_bwd_multi(
-                Xg, [(P["We"], xp_g if ym else None, dxp_g, am, 0, True), (P["Wc"], None, dH_g, 0, 1, False)])
-            _, g["Wk"], g["bk"] = kern.linear_bwd(x_local, P["Wk"], s["xk"] if ym else None, dxk, am, 0, False, True)
-            dX1 = dX2 = dX3 = None
+        elif not self.x_grad and same_rows:
+            # one pass over X for the three weight gradients
+            (g["We"], g["be"]), (g["Wk"], g["bk"]), (g["Wc"], _) = self._linear_bwd_multi(Xg, [le, lk, (P["Wc"], None, dH_g, 0, 1, False)])
+        elif not self.x_grad:
+            (g["We"], g["be"]), (g["Wc"], _) = self._linear_bwd_multi(Xg, [le, (P["Wc"], None, dH_g, 0, 1, False)])
+            _, g["Wk"], g["bk"] = kern.linear_bwd(x_local, *lk[:5], False, True)
         else:
-            dX1, g["We"], g["be"] = kern.linear_bwd(Xg, P["We"], xp_g, dxp_g, 1, 0, self.x_grad, True)
-            dX3, g["Wc"], _ = kern.linear_bwd(Xg, P["Wc"], None, dH_g, 0, 1, self.x_grad, False)
-            dX2, g["Wk"], g["bk"] = kern.linear_bwd(x_local, P["Wk"], s["xk"], dxk, 1, 0, self.x_grad, True)
+            dX1, g["We"], g["be"] = kern.linear_bwd(Xg, P["We"], xp_g, dxp_g, 1, 0, True, True)
+            dX3, g["Wc"], _ = kern.linear_bwd(Xg, P["Wc"], None, dH_g, 0, 1, True, False)
+            dX2, g["Wk"], g["bk"] = kern.linear_bwd(x_local, P["Wk"], s["xk"], dxk, 1, 0, True, True)
         if self.coll:
             # (the edge-MLP scorer's gradients -- g["scorer"], every rank's share of the selected edges -- ride in the same bucket)
             sg = g.get("scorer")

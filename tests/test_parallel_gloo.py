@@ -14,9 +14,12 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from dgg_amd.parallel import KernelContract  # noqa: E402
 
 
-class CpuKern:
+class CpuKern(KernelContract):
     """numpy restatement of the dgg_amd.ops signatures used by ShardedDGGConv (test stand-in only)."""
 
     @staticmethod
