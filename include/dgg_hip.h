@@ -314,6 +314,26 @@ int dgg_allpairs_mlp_topk(const float *AB, const float *xp, int64_t N, int h, in
                           int ex_mode, float t_ex, const float *wdu, const float *wdv, const float *wex, const float *b1,
                           const float *w2, const float *b2, int act, int noise_mode, const float *G, int64_t ldG, uint32_t s0,
                           uint32_t s1, int K, int32_t *idx, float *val, float *ex_out, void *stream);
+/* dgg_allpairs_mlp_topk for rows of ANY width, on CHUNKED rows with the ramp fused.  The reference ramps over the whole dense row
+ * (select_top_k, dgm.py:1402-1421) of scores the edge-MLP scorers produce (dgm.py:1645-1719, perturbed as dgm.py:1211-1229) with an
+ * unbounded learned degree k = relu(...) + 1 (dgm.py:1580-1584); here row i keeps its L_i = ceil(k_i + 8.5) + 1 best columns (cut to
+ * 64 M_i; all N columns when L_i > N) in the chunks [cptr[i], cptr[i+1]) of idx / val / ex_out / w [ccap,64].  k [row1-row0] and
+ * cptr [row1-row0+1] (dgg_chunk_layout of those k) belong to the rows asked for; maxm >= max M_i; AB, xp, deg, G and the noise key are
+ * every node's (the noise is keyed on the GLOBAL row).  Same score bits and key order (score descending, lower column first, the self
+ * column included) as dgg_allpairs_mlp_topk: with every M_i = 1, idx / val / ex_out equal its output at K = 64 on the ranks below L_i.
+ * Every other slot of a row's chunks and every chunk in [cptr[rows], ccap) is written EMPTY (idx -1, val 0, ex_out 0, w 0); nothing
+ * outside the arrays is written.  w and rs [row1-row0] (both nullable, together) carry the bits of dgg_allpairs_topk_ranked_wide's ramp:
+ * mode 0 score x ramp, 1 the ramp, 3 the straight-through forward value; rs = lane-wise sums over a row's chunks, then the wavefront
+ * butterfly.  ex_out (nullable) as dgg_allpairs_mlp_topk.  A wavefront settles 8 chunks of a row per sweep over the columns; rows of more
+ * chunks take ceil(maxm / 8) sweeps launched from the host integer maxm (no device read-back), each continuing strictly below the last
+ * key the previous one wrote.
+ * Refusals (codes, nothing written) as dgg_allpairs_mlp_topk: DGG_ERR_UNSUPPORTED for hw or h outside {16, 32, 64, 128}, ex_mode 1,
+ * DGG_NOISE_RANKED / RANKED_SYM; DGG_ERR_ARG for the rest, and for a mode outside {0, 1, 3}. */
+int dgg_allpairs_mlp_topk_wide(const float *AB, const float *xp, int64_t N, int h, int hw, int64_t row0, int64_t row1, const float *deg,
+                               int ex_mode, float t_ex, const float *wdu, const float *wdv, const float *wex, const float *b1,
+                               const float *w2, const float *b2, int act, int noise_mode, const float *G, int64_t ldG, uint32_t s0,
+                               uint32_t s1, const float *k, int mode, int maxm, const int32_t *cptr, int64_t ccap, int32_t *idx,
+                               float *val, float *ex_out, float *w, float *rs, void *stream);
 /* autograd of dgg_edge_mlp_fwd for the selected entries: dval (wrt the stored score) -> dAB [N,2*hw] and
  * dpar [5*hw+1] = [dwdu | dwdv | dwex | db1 | dw2 | db2] (both ACCUMULATED into: caller zeroes), dex [N,K] (nullable,
  * overwritten; gradient wrt the per-edge extra).  ex [E] as written by the forward (nullable when ex_mode was 0). */
@@ -328,6 +348,16 @@ int dgg_edge_mlp_bwd_rows(const float *AB, int64_t N, int hw, int64_t row0, int6
                           const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
                           const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
                           int perturb, float *dAB, float *dpar, float *dex, void *stream);
+/* dgg_edge_mlp_bwd_rows with DETERMINISTIC parameter sums (the reference sums dense tensors in autograd, dgm.py:1628-1725; the two
+ * entries above add one partial sum per workgroup to dpar with float atomics, in whatever order the workgroups finish).  Here every
+ * workgroup stores its 5*hw + 1 sums as a row of ws (5*hw + 2 floats: db2's sum, kept in double from the entry on, as a float pair)
+ * and a second kernel adds the rows in ascending order in double: dpar has the same bits in every run.
+ * ws: ws_floats >= 5*hw + 2 floats of scratch; min(ceil((row1 - row0) / 4), 1024) rows of 5*hw + 2 floats keep
+ * every workgroup of the atomic form, fewer rows launch fewer workgroups.  dAB's neighbour side still uses float atomics. */
+int dgg_edge_mlp_bwd_det(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *idx,
+                         const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
+                         const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
+                         int perturb, float *dAB, float *dpar, float *dex, float *ws, int64_t ws_floats, void *stream);
 /* the same for an ELL block whose payload partition (dgg_partp_build of (idx, w), with its entry -> record map: dgg_partp_has_map(N))
  * is at hand: the neighbour-side sums d B_j WITHOUT float atomics -- every selected entry's term is stored as a row of dz_rec in
  * record order (the records of a destination node are consecutive) and a second kernel adds each node's rows.  w [N,K]: the weights
@@ -515,6 +545,12 @@ int dgg_norm_bwd_da(const int32_t *idx, const float *w, const float *rs, const f
  * mode 2: no ramp (dval = dw, dk untouched, val/k may be NULL): plain normalize_adj backward */
 int dgg_softk_bwd(const int32_t *idx, const float *val, const float *k, const float *rs, const float *dA, const float *da,
                   int64_t N, int K, int64_t row0, int mode, int normalized, float *dval, float *dk, void *stream);
+/* dgg_softk_bwd (not normalised, mode 0 / 1) on CHUNKED rows -- the ramp backward of select_top_k over a dense row of any width
+ * (dgm.py:1402-1421): dw [ccap,64] (cotangent of w) -> dval [ccap,64] (overwritten on all ccap chunks; 0 on empty slots and on the
+ * chunks beyond cptr[rows]) and dk [rows], with rank = 64 (chunk - cptr[i]) + lane.  One wavefront per node: dk needs no atomics and is
+ * deterministic.  val may be NULL in mode 1. */
+int dgg_softk_bwd_chunked(const int32_t *idx, const float *val, const float *k, const float *dw, int64_t rows, const int32_t *cptr,
+                          int64_t ccap, int mode, float *dval, float *dk, void *stream);
 /* the same for a NORMALISED adjacency whose `da_cols` (GLOBAL length) holds the neighbour-side sums only -- what the column
  * kernels of the partitioned backward leave (dgg_ell_conv_bwd_partp) -- the row side rs_i^1/2 sum_r dA_ir ahat_ir is formed inside
  * (ahat_rows [N,K]: the normalised values).  Reference: autograd of normalize_adj + select_top_k, model.py:1205-1219, dgm.py:1402-1421 */

@@ -62,10 +62,13 @@ PROTOTYPES = {
     "dgg_edge_mlp_fwd": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "dgg_allpairs_mlp_topk": [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _u32, _u32,
                               _i32, _vp, _vp, _vp, _vp],
+    "dgg_allpairs_mlp_topk_wide": [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _u32,
+                                   _u32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     "dgg_edgelist_topk_p": [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _u32, _u32, _i32, _vp, _vp, _vp, _vp],
     "dgg_edgelist_topk_p_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _u32, _u32, _i32, _vp, _vp, _vp, _vp],
     "dgg_edge_mlp_bwd": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "dgg_edge_mlp_bwd_rows": [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "dgg_edge_mlp_bwd_det": [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
     "dgg_edge_mlp_bwd_partp": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
     "dgg_edge_mlp_bwd_partp_rows": [_vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "dgg_csr_softk_fwd": [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _u32, _u32, _i32, _vp, _vp, _vp, _vp],
@@ -107,6 +110,7 @@ PROTOTYPES = {
     "dgg_ell_spmm_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
     "dgg_norm_bwd_da": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp],
     "dgg_softk_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp],
+    "dgg_softk_bwd_chunked": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp],
     "dgg_softk_bwd_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp],
     "dgg_part_ws_bytes": [_i64, _i32, _i64],
     "dgg_part_build": [_vp, _vp, _i64, _i32, _i64, _vp, _vp],

@@ -105,6 +105,15 @@ __device__ __forceinline__ float c_ramp(float r, float k) {
     a = __fmul_rn(0.5f, a);
     return __fadd_rn(1.0f, -a);
 }
+// weight of rank r of a row with learned degree k and score sv (dgm.py:1410-1420): mode 0 score x ramp, 1 the ramp alone, 3 the
+// straight-through forward value (ramp - score x ramp) + score x ramp.  The ONE copy the searches that fuse the ramp on chunked rows share
+// (dgg_allpairs_topk_ranked_wide, dgg_allpairs_mlp_topk_wide): their weights cannot differ in a bit.
+__device__ __forceinline__ float ramp_weight(int r, float k, float sv, int softk_mode) {
+    const float f = c_ramp((float)r, k);
+    if (softk_mode != 0 && softk_mode != 3) return f;
+    const float a = __fmul_rn(sv, f);
+    return softk_mode == 0 ? a : __fadd_rn(__fadd_rn(f, -a), a);
+}
 
 // ---- counter-based noise ---------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
@@ -242,6 +251,10 @@ __device__ __forceinline__ float bcast(float v, int uniform_lane) {
     return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), uniform_lane));
 }
 __device__ __forceinline__ int32_t bcast(int32_t v, int uniform_lane) { return __builtin_amdgcn_readlane(v, uniform_lane); }
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int uniform_lane) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), uniform_lane) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, uniform_lane);
+}
 
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
     uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);

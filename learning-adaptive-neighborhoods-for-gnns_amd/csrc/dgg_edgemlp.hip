@@ -137,13 +137,15 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
     const float *__restrict__ wex, const float *__restrict__ b1, const float *__restrict__ w2,
     const float *__restrict__ b2, int act, int perturb, float *__restrict__ dAB, float *__restrict__ dpar,
     float *__restrict__ dex, const float *__restrict__ wrow = nullptr, const int *__restrict__ recpos = nullptr,
-    float *__restrict__ dz_rec = nullptr, int64_t dz_rows = 0) {
+    float *__restrict__ dz_rec = nullptr, int64_t dz_rows = 0, float *__restrict__ part = nullptr) {
+    // part [gridDim.x][5*hw + 2] (dgg_edge_mlp_bwd_det; the last float is the low part of db2's sum): every workgroup STORES its parameter sums there instead of adding them to dpar
+    // with float atomics; edge_mlp_parsum adds the workgroups' rows in a fixed order.
     // dz_rec (VEC 4, ELL rows; dgg_edge_mlp_bwd_partp): the neighbour-side term d z of every selected entry goes, as ONE 16-byte store
     // per lane, to row recpos[entry] of dz_rec -- the entry's place among the destination-ordered records of the payload partition,
     // where the records of a node are consecutive -- and edge_mlp_colsum adds each node's rows; without it: hw float atomics per entry
     // onto dAB (6.9 M at the Pubmed shape: most of the kernel's time).  wrow: the weights the partition was built from (an entry has a
     // record iff idx >= 0 and w != 0); an entry with a record but no cotangent gets a zero row.
-    extern __shared__ float red[];                               // [4 waves][5*hw + 1]
+    extern __shared__ float red[];                               // [4 waves][5*hw + 1] floats, then [4 waves] doubles (db2)
     const int LPE = hw / VEC, EPI = 64 / LPE;
     const int lane = threadIdx.x & 63, wave = dgg::wave_id(), c = lane % LPE, slot = lane / LPE;
     const int o0 = c * VEC;
@@ -154,7 +156,10 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
         b1_r[q] = b1[o0 + q]; w2_r[q] = w2[o0 + q];
     }
     const float b2v = b2[0];
-    float g_wdu[VEC] = {}, g_wdv[VEC] = {}, g_wex[VEC] = {}, g_b1[VEC] = {}, g_w2[VEC] = {}, g_b2 = 0.0f;
+    float g_wdu[VEC] = {}, g_wdv[VEC] = {}, g_wex[VEC] = {}, g_b1[VEC] = {}, g_w2[VEC] = {};
+    // db2 is ONE number summed over every entry, with heavy cancellation: in double from the entry to the workgroup's sum (one add per
+    // batch; float left it several ulps off at a few ten thousand entries)
+    double g_b2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < N; i += (int64_t)gridDim.x * 4) {
         const int64_t u = row0 + i;                              // (i: the block's row, u: its node -- the row side of AB / deg / dAB)
         float Ai[VEC], dA[VEC] = {};
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
                 for (int q = 0; q < VEC; q++)
                     if (dzv[q] != 0.0f) atomicAdd(dAB + (int64_t)j * 2 * hw + hw + o0 + q, dzv[q]);
             }
-            if (c == 0) g_b2 += ds;
+            if (c == 0) g_b2 += (double)ds;
             if (dex) {
                 for (int off = 1; off < LPE; off <<= 1) de += __shfl_xor(de, off, 64);
                 if (c == 0 && r < cnt) dex[en] = de;
@@ -284,6 +289,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
         g_b2 += __shfl_xor(g_b2, off, 64);
     }
     const int NP = 5 * hw + 1;
+    double *redd = reinterpret_cast<double *>(red + 4 * NP);       // (4 NP is even: 8-byte aligned)
     if (slot == 0) {
         float *mine = red + wave * NP;
 #pragma unroll
@@ -291,16 +297,68 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
             mine[o0 + q] = g_wdu[q]; mine[hw + o0 + q] = g_wdv[q]; mine[2 * hw + o0 + q] = g_wex[q];
             mine[3 * hw + o0 + q] = g_b1[q]; mine[4 * hw + o0 + q] = g_w2[q];
         }
-        if (c == 0) mine[5 * hw] = g_b2;
+        if (c == 0) redd[wave] = g_b2;
     }
     __syncthreads();
     for (int e = threadIdx.x; e < NP; e += 256) {
-        const float t = (red[e] + red[NP + e]) + (red[2 * NP + e] + red[3 * NP + e]);
-        if (t != 0.0f) atomicAdd(dpar + e, t);
+        float t = (red[e] + red[NP + e]) + (red[2 * NP + e] + red[3 * NP + e]);
+        if (e == NP - 1) {                                           // db2: the workgroup's double sum, as a float pair (hi, lo) for part
+            const double tb = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+            t = (float)tb;
+            if (part) part[(int64_t)blockIdx.x * (NP + 1) + NP] = (float)(tb - (double)t);
+        }
+        if (part) part[(int64_t)blockIdx.x * (NP + 1) + e] = t;
+        else if (t != 0.0f) atomicAdd(dpar + e, t);
     }
 }
 
+// dpar[e] += the sum over the nblk workgroups of part[b][e] (rows of NP + 1 floats: db2 = element NP - 1 has its low part at NP), b
+// ascending, in double: the same bits in every run, and no rounding
+// between the workgroups' sums (at most 1024 of them) beyond the final one
+__global__ __launch_bounds__(64) void edge_mlp_parsum(const float *__restrict__ part, int nblk, int NP, float *__restrict__ dpar) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= NP) return;
+    double s = 0.0;
+    for (int b = 0; b < nblk; b++) s += (double)part[(int64_t)b * (NP + 1) + e];
+    if (e == NP - 1)
+        for (int b = 0; b < nblk; b++) s += (double)part[(int64_t)b * (NP + 1) + NP];
+    dpar[e] += (float)s;
+}
+
 bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
+
+// the launch behind dgg_edge_mlp_bwd_rows (ws == nullptr: parameter sums by float atomics) and dgg_edge_mlp_bwd_det (ws: rows of ws)
+int edge_mlp_bwd_launch(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *idx,
+                        const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
+                        const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
+                        int perturb, float *dAB, float *dpar, float *dex, float *ws, int64_t ws_floats, void *stream) {
+    if (!rowptr && (K < 1 || K > 64)) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ELL width K must be in [1,64]");
+    const int vec = hw % 4 == 0 ? 4 : 1;
+    const int lpe = hw / vec;
+    if (!pow2(lpe) || lpe > 64)
+        return dgg_set_error(DGG_ERR_UNSUPPORTED, "edge_mlp_bwd: hidden width must be 1, 2 or 4 x a power of two (<= 256)");
+    if ((ex && (!wex || (!eid && !rowptr))) || (deg && (!wdu || !wdv)))
+        return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd: missing extras / weights");
+    if (row0 < 0 || row1 < row0 || row1 > N) return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd: rows must satisfy 0 <= row0 <= row1 <= N");
+    const int64_t rows = row1 - row0;
+    if (rows == 0) return 0;
+    static const int64_t gmax = getenv("DGG_EMLP_GRID") ? atoll(getenv("DGG_EMLP_GRID")) : 1024;   // (Pubmed shape: 103 us at 2048 workgroups, 85-89 at 512-1024, 123 at 128: row latency against contended parameter sums)
+    unsigned grid = (unsigned)((rows + 3) / 4 < gmax ? (rows + 3) / 4 : gmax);
+    const int NP = 5 * hw + 1;
+    if (ws && grid > ws_floats / (NP + 1)) grid = (unsigned)(ws_floats / (NP + 1));      // (one row of ws per workgroup; the row loop strides by the grid)
+    const size_t lds = (size_t)4 * (5 * hw + 1) * sizeof(float) + 4 * sizeof(double);
+    if (vec == 4)
+        hipLaunchKernelGGL(edge_mlp_bwd_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, rowptr, idx, eid, val,
+                           dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex, (const float *)nullptr, (const int *)nullptr,
+                           (float *)nullptr, (int64_t)0, ws);
+    else
+        hipLaunchKernelGGL(edge_mlp_bwd_kernel<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, rowptr, idx, eid, val,
+                           dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex, (const float *)nullptr, (const int *)nullptr,
+                           (float *)nullptr, (int64_t)0, ws);
+    if (ws)
+        hipLaunchKernelGGL(edge_mlp_parsum, dim3((unsigned)((NP + 63) / 64)), dim3(64), 0, (hipStream_t)stream, ws, (int)grid, NP, dpar);
+    return dgg_check_launch("edge_mlp_bwd");
+}
 
 }  // namespace
 
@@ -372,26 +430,21 @@ int dgg_edge_mlp_bwd_rows(const float *AB, int64_t N, int hw, int64_t row0, int6
                           const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
                           const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
                           int perturb, float *dAB, float *dpar, float *dex, void *stream) {
-    if (!rowptr && (K < 1 || K > 64)) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ELL width K must be in [1,64]");
-    const int vec = hw % 4 == 0 ? 4 : 1;
-    const int lpe = hw / vec;
-    if (!pow2(lpe) || lpe > 64)
-        return dgg_set_error(DGG_ERR_UNSUPPORTED, "edge_mlp_bwd: hidden width must be 1, 2 or 4 x a power of two (<= 256)");
-    if ((ex && (!wex || (!eid && !rowptr))) || (deg && (!wdu || !wdv)))
-        return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd: missing extras / weights");
-    if (row0 < 0 || row1 < row0 || row1 > N) return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd: rows must satisfy 0 <= row0 <= row1 <= N");
-    const int64_t rows = row1 - row0;
-    if (rows == 0) return 0;
-    static const int64_t gmax = getenv("DGG_EMLP_GRID") ? atoll(getenv("DGG_EMLP_GRID")) : 1024;   // (Pubmed shape: 103 us at 2048 workgroups, 85-89 at 512-1024, 123 at 128: row latency against contended parameter sums)
-    const unsigned grid = (unsigned)((rows + 3) / 4 < gmax ? (rows + 3) / 4 : gmax);
-    const size_t lds = (size_t)4 * (5 * hw + 1) * sizeof(float);
-    if (vec == 4)
-        hipLaunchKernelGGL(edge_mlp_bwd_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, rowptr, idx, eid, val,
-                           dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex);
-    else
-        hipLaunchKernelGGL(edge_mlp_bwd_kernel<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, rowptr, idx, eid, val,
-                           dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex);
-    return dgg_check_launch("edge_mlp_bwd");
+    return edge_mlp_bwd_launch(AB, N, hw, row0, row1, rowptr, idx, eid, val, dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB,
+                               dpar, dex, nullptr, 0, stream);
+}
+
+// dgg_edge_mlp_bwd_rows with DETERMINISTIC parameter sums: the workgroups store their sums of dpar's 5*hw + 1 elements as rows of ws
+// (5*hw + 2 floats each: db2's sum as a float pair; ws_floats >= 5*hw + 2; min(ceil(rows / 4), 1024) rows of that length use every workgroup the atomic form would launch, fewer rows
+// mean fewer workgroups) and a second kernel adds the rows in a fixed order in double.  dAB's neighbour side keeps its float atomics.
+int dgg_edge_mlp_bwd_det(const float *AB, int64_t N, int hw, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *idx,
+                         const int32_t *eid, const float *val, const float *dval, int K, const float *deg, const float *ex, const float *wdu,
+                         const float *wdv, const float *wex, const float *b1, const float *w2, const float *b2, int act,
+                         int perturb, float *dAB, float *dpar, float *dex, float *ws, int64_t ws_floats, void *stream) {
+    if (!ws || hw < 1 || ws_floats < 5 * (int64_t)hw + 2)
+        return dgg_set_error(DGG_ERR_ARG, "edge_mlp_bwd_det: workspace of at least 5 hw + 2 floats required");
+    return edge_mlp_bwd_launch(AB, N, hw, row0, row1, rowptr, idx, eid, val, dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB,
+                               dpar, dex, ws, ws_floats, stream);
 }
 
 // dgg_edge_mlp_bwd for an ELL block whose PAYLOAD PARTITION is at hand (dgg_partp_build of (idx, w) with the entry -> record map:
@@ -426,7 +479,7 @@ int dgg_edge_mlp_bwd_partp_rows(const float *AB, int64_t N, int hw, int64_t row0
     if (rows == 0) return 0;
     static const int64_t gmax = getenv("DGG_EMLP_GRID") ? atoll(getenv("DGG_EMLP_GRID")) : 1024;
     const unsigned grid = (unsigned)((rows + 3) / 4 < gmax ? (rows + 3) / 4 : gmax);
-    const size_t lds = (size_t)4 * (5 * hw + 1) * sizeof(float);
+    const size_t lds = (size_t)4 * (5 * hw + 1) * sizeof(float) + 4 * sizeof(double);
     hipLaunchKernelGGL(edge_mlp_bwd_kernel<4>, dim3(grid), dim3(256), lds, (hipStream_t)stream, AB, rows, row0, hw, (const int64_t *)nullptr, idx, eid,
                        val, dval, K, deg, ex, wdu, wdv, wex, b1, w2, b2, act, perturb, dAB, dpar, dex, w, recpos, dz_rec, dz_rows);
     hipLaunchKernelGGL(edge_mlp_colsum, dim3((unsigned)((N * lpe + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nodeptr, N, dz_rec, dz_rows,

@@ -586,6 +586,40 @@ __global__ __launch_bounds__(WPB * 64) void softk_bwd_kernel(const int32_t *__re
     if (lane == 0 && dk) dk[i] = skp;
 }
 
+// softk_bwd_kernel (not normalised, modes 0 / 1) on CHUNKED rows: one wavefront per NODE walks its chunks [cptr[i], cptr[i+1]); the rank
+// of lane l of the row's m-th chunk is 64 m + l.  dk_i is the wavefront's own sum: no atomics, the same bits on every run.  Empty slots
+// get dval = 0; the workgroups beyond the rows zero dval on the spare chunks [cptr[rows], ccap).
+__global__ __launch_bounds__(WPB * 64) void softk_bwd_chunked_kernel(const int32_t *__restrict__ idx, const float *__restrict__ val,
+                                                                    const float *__restrict__ k, const float *__restrict__ dw,
+                                                                    int64_t rows, const int32_t *__restrict__ cptr, int64_t ccap, int mode,
+                                                                    float *__restrict__ dval, float *__restrict__ dk, unsigned nrow_blocks) {
+    const int lane = threadIdx.x & 63;
+    if (blockIdx.x >= nrow_blocks) {
+        const int64_t q = (int64_t)cptr[rows] + (int64_t)(blockIdx.x - nrow_blocks) * WPB + dgg::wave_id();
+        if (q < ccap) dval[q * 64 + lane] = 0.0f;
+        return;
+    }
+    const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
+    if (i >= rows) return;
+    const int c0 = cptr[i], c1 = cptr[i + 1];
+    const float ki = k[i];
+    float skp = 0.0f;
+    for (int c = c0; c < c1 && c < ccap; c++) {
+        const int64_t e = (int64_t)c * 64 + lane;
+        const bool live = idx[e] >= 0;
+        const float g = dw[e];
+        const float v = mode == 0 ? val[e] : 0.0f;
+        const float th = c_tanh((float)(64 * (c - c0) + lane) - ki);
+        const float f = 1.0f - 0.5f * (1.0f + th);
+        const float dfdk = 0.5f * (1.0f - th * th);
+        skp += live ? (mode == 0 ? g * v * dfdk : g * dfdk) : 0.0f;
+        dval[e] = (live && mode == 0) ? g * f : 0.0f;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) skp += __shfl_xor(skp, off, 64);
+    if (lane == 0) dk[i] = skp;
+}
+
 // score backward: dval (wrt the stored score) -> dxp (fp32 atomics; dxp zeroed by caller).  Features on lanes.
 __global__ __launch_bounds__(WPB * 64) void edge_bwd_kernel(const float *__restrict__ xp, int64_t N, int h,
                                                            const int32_t *__restrict__ idx, const float *__restrict__ val,
@@ -1174,6 +1208,19 @@ int dgg_softk_bwd(const int32_t *idx, const float *val, const float *k, const fl
     hipLaunchKernelGGL(softk_bwd_kernel, dim3(rows_grid(N)), dim3(WPB * 64), 0, (hipStream_t)stream, idx, val, k, rs, dA, da,
                        N, K, row0, mode, normalized, dval, dk, (const float *)nullptr);
     return dgg_check_launch("softk_bwd");
+}
+
+int dgg_softk_bwd_chunked(const int32_t *idx, const float *val, const float *k, const float *dw, int64_t rows, const int32_t *cptr,
+                          int64_t ccap, int mode, float *dval, float *dk, void *stream) {
+    if (mode != 0 && mode != 1) return dgg_set_error(DGG_ERR_ARG, "softk_bwd_chunked: mode must be 0 (k_times_edge_prob) or 1 (k_only)");
+    if (rows < 0 || ccap < 0 || ccap >= ((int64_t)1 << 25)) return dgg_set_error(DGG_ERR_ARG, "softk_bwd_chunked: rows >= 0, 0 <= ccap < 2^25 chunks");
+    if (rows == 0) return 0;
+    if (!idx || (mode == 0 && !val) || !k || !dw || !cptr || !dval || !dk) return dgg_set_error(DGG_ERR_ARG, "softk_bwd_chunked: missing operand");
+    const unsigned nrow_blocks = rows_grid(rows);
+    const int64_t tail = ccap > rows ? ccap - rows : 0;         // (every row has at least one chunk, or the capacity is used up)
+    hipLaunchKernelGGL(softk_bwd_chunked_kernel, dim3(nrow_blocks + rows_grid(tail)), dim3(WPB * 64), 0, (hipStream_t)stream, idx, val, k, dw,
+                       rows, cptr, ccap, mode, dval, dk, nrow_blocks);
+    return dgg_check_launch("softk_bwd_chunked");
 }
 
 int dgg_softk_bwd_rows(const int32_t *idx, const float *val, const float *k, const float *rs, const float *dA, const float *da_cols,

@@ -404,11 +404,6 @@ __global__ __launch_bounds__(CL_T) void chunk_layout(const float *__restrict__ k
     }
 }
 
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int uniform_lane) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), uniform_lane) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, uniform_lane);
-}
-
 // The search of allpairs_topk_ranked with M_i <= MAXM descending 64-lane lists per row in registers (list[0] holds ranks 0..63, list[1]
 // ranks 64..127, ...).  A block's live keys are sorted and cascaded down the lists: merged with list[m] by one bitonic half-cleaner
 // (upper 64 stay, lower 64 carry on to list[m+1]); a list whose smallest key beats the carry's largest is skipped, and the cascade ends
@@ -562,13 +557,7 @@ __global__ __launch_bounds__(256) void allpairs_topk_ranked_wide(const float *__
             const float sv = empty ? 0.0f : key_val(list[m]);
             val[e] = sv;
             if (w_out) {
-                const float f = c_ramp((float)r, ki);
-                float v = f;
-                if (softk_mode == 0 || softk_mode == 3) {
-                    const float a = __fmul_rn(sv, f);
-                    v = softk_mode == 0 ? a : __fadd_rn(__fadd_rn(f, -a), a);
-                }
-                const float wv = empty ? 0.0f : v;
+                const float wv = empty ? 0.0f : ramp_weight(r, ki, sv, softk_mode);
                 w_out[e] = wv;
                 rsum = m == 0 ? wv : __fadd_rn(rsum, wv);
             }

@@ -298,6 +298,46 @@ class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
         return (dx, dk, None, dWe, dbe) + gsc + (None,)
 
 
+class _DGGAllPairsMlpWideAdjFn(torch.autograd.Function):
+    """_DGGAllPairsMlpAdjFn on CHUNKED rows: learned degrees beyond the 64-rank list (the reference ramps over the whole dense row with
+    an unbounded degree, dgm.py:1402-1421, 1580-1584).  Forward: dgg_allpairs_mlp_topk_wide on cfg["layout"] (ops.chunk_layout) -- row i
+    keeps ceil(k_i + 8.5) + 1 ranks in chunks of 64, the ramp fused.  Backward: the ramp on chunked rows (softk_bwd_chunked), then the
+    edge-list node's scorer backward in its CSR form on the flattened chunks (row i's entries are [64 cptr[i], 64 cptr[i+1]); empty
+    slots carry idx = -1 and are skipped), the distance term of u-v-deg-dist through csr_uvdist_bwd on the same pattern."""
+
+    @staticmethod
+    def forward(ctx, x, k, deg, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
+        xp = ops.linear_fwd(x, We, be, ops.ACT_LEAKY)
+        AB = ops.linear_fwd(xp, Wcat, None, ops.ACT_NONE)
+        sdeg = deg if wdu is not None else None
+        lay = cfg["layout"]
+        idx, val, ex, w, rs = ops.allpairs_mlp_topk_wide(AB, xp, sdeg, cfg["ex_mode"], cfg["t_ex"], wdu, wdv, wex, eb1, w2, b2, cfg["act"], k, lay,
+                                                         cfg.get("fwd_mode", cfg["mode"]), cfg["noise_mode"], cfg["G"], cfg["seed"])
+        ctx.cfg = cfg
+        ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in (sdeg, ex, wdu, wdv, wex))
+        ctx.save_for_backward(x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2)
+        ctx.mark_non_differentiable(idx, val, rs)
+        return w, idx, val, rs
+
+    @staticmethod
+    def backward(ctx, dw, *_):
+        x, We, xp, k, idx, val, AB, *terms = ctx.saved_tensors
+        cfg = ctx.cfg
+        lay = cfg["layout"]
+        dval, dk = ops.softk_bwd_chunked(idx, val, k, dw.contiguous(), lay, cfg["mode"])
+        rowptr = lay.cptr.to(torch.int64) * 64
+        col = idx.reshape(-1)
+        ex = None if ctx.opt[1] is None else ctx.opt[1].reshape(-1)
+        dxp, dex, gsc = _mlp_score_bwd(ctx, terms, xp, AB, col, None, val.reshape(-1), dval.reshape(-1), ex, cfg["noise_mode"] != ops.NOISE_NONE, 5,
+                                       rowptr=rowptr)
+        if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
+            # (empty slots: ex = 0 from the forward and dex = 0 from edge_mlp_bwd's CSR form, so csr_uvdist_bwd skips them before it reads
+            #  the column; the clamp only keeps a column it never uses inside the graph)
+            dxp = dxp + ops.csr_uvdist_bwd(xp, rowptr, col.clamp(min=0), ex, dex, t=cfg["t_ex"])
+        dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
+        return (dx, dk, None, dWe, dbe) + gsc + (None,)
+
+
 class _DGGScoresFn(torch.autograd.Function):
     """Raw edge probabilities on the stored entries of in_adj, CSR order (reference edge_prob_net, dgm.py:1607-1725), for the
     forward variants that return them as the adjacency: debug_step 0 / 1 (dgm.py:1202-1209, 1240-1246) and the k-select mode
@@ -588,7 +628,8 @@ class DGG_LearnableK_debug(nn.Module):
                 "candidates than that: ranks the reference still weights were dropped (row sums, normalisation and gradients "
                 "differ from the reference from here on).  Edge-list candidates: set args.dgg_wide_rows = 'csr' (rows of any width; "
                 "'auto' picks it whenever a row would lose weight, except inside a hipGraph capture).  All-pairs candidates: "
-                "args.dgg_wide_rows = 'auto' keeps every weighted rank in chunked rows (ranked noise generator; one eager forward before a capture).")
+                "args.dgg_wide_rows = 'auto' keeps every weighted rank in chunked rows (ranked noise generator; one eager forward before a capture); "
+                "under the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv args.dgg_allpairs_mlp_rows = 'chunked' does.")
 
     def _sym_generator_now(self):
         """generator for symmetric noise in the next forward: "ranked" | "hash".  args.dgg_sym_generator: "ranked" (default), "hash", or
@@ -898,22 +939,50 @@ class DGG_LearnableK_debug(nn.Module):
     def wide_row_plan(self, N, all_pairs, noise_mode):
         """What rows that need more than 64 ranks do for a graph of N nodes under args.dgg_wide_rows -- the ONE summary of the policy
         (the predicates the forwards use: _chunk_policy, _wide_rows_state, _allpairs_wide):
-          "chunked"          all-pairs candidates: ceil(k_i + 8.5) + 1 ranks of every row in chunks of 64, any width (auto / chunked)
+          "chunked"          all-pairs candidates: ceil(k_i + 8.5) + 1 ranks of every row in chunks of 64, any width (auto / chunked;
+                             the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv: with args.dgg_allpairs_mlp_rows = "chunked",
+                             whatever args.dgg_wide_rows says -- except inside a hipGraph capture, where nothing can be read back:
+                             a captured forward keeps the list and its enforced bound although the answer here is "chunked")
           "csr"              the CSR form of select_top_k from the first forward (csr)
           "csr_when_needed"  the CSR form from the forward whose learned degrees first need it, and from then on (auto on edge lists
                              and for explicit noise tensors on small all-pairs graphs; csr_auto)
           "list"             64 ranks per row, the bound enforced by check_ell_bound (ell; graphs beyond dgg_allpairs_csr_max without a
-                             chunked form; the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv on all-pairs candidates)"""
+                             chunked form; the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv on all-pairs candidates unless
+                             args.dgg_allpairs_mlp_rows = "chunked")"""
         policy = getattr(self.args, "dgg_wide_rows", "auto")
         if not all_pairs:
             return {"ell": "list", "csr": "csr"}.get(policy, "csr_when_needed")
         if self._chunk_policy(noise_mode):
             return "chunked"
-        if self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS:     # (the edge-MLP scorers on all-pairs candidates have the list only)
-            return "list"
+        if self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS:     # (the edge-MLP scorers on all-pairs candidates: an opt-in of their own)
+            return "chunked" if self._allpairs_mlp_chunked() else "list"
         if policy in ("ell", "chunked") or N > int(getattr(self.args, "dgg_allpairs_csr_max", 8192)):
             return "list"
         return "csr" if policy == "csr" else "csr_when_needed"
+
+    def _allpairs_mlp_chunked(self):
+        """All-pairs rows wider than the 64-rank list as chunked rows under the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv?
+        (Asked by callers that have already established that scorer on all-pairs candidates.)
+        args.dgg_allpairs_mlp_rows: "list" (default: 64 ranks, the bound enforced by check_ell_bound) / "chunked" (any learned degree:
+        dgg_allpairs_mlp_topk_wide; one layout read-back per forward).  An argument of its own: args.dgg_wide_rows keeps its meaning
+        for every other configuration.  Under a hipGraph capture nothing can be read back: the list and its bound stay.
+        "chunked" needs the full list width (ell_width = 64: a chunk is 64 ranks); with a narrower list it raises."""
+        rows = getattr(self.args, "dgg_allpairs_mlp_rows", "list")
+        if rows not in ("list", "chunked"):
+            raise ValueError(f"args.dgg_allpairs_mlp_rows must be 'list' or 'chunked', not {rows!r}")
+        if rows == "chunked" and self.ell_width != 64:
+            raise ValueError(f"args.dgg_allpairs_mlp_rows = 'chunked' needs args.dgg_ell_width = 64 (chunks of 64 ranks), not {self.ell_width}")
+        return rows == "chunked"
+
+    @staticmethod
+    def _log_first_k_chunked(writer, epoch, cfg, w, val, lay):
+        """the two scalars the reference logs from inside the DGG (dgm.py:1259-1261), on chunked rows"""
+        if writer is None:
+            return
+        f = w.detach() if (cfg["mode"] == ops.MODE_K_ONLY or "fwd_mode" in cfg) else (w.detach() / val.clamp(min=1e-30))
+        fs = torch.zeros(lay.rows, device=w.device).index_add_(0, lay.cnode.long(), f.sum(-1))
+        writer.add_scalar("values/first_k_std", fs.std(), epoch)
+        writer.add_scalar("values/first_k_mean", fs.mean(), epoch)
 
     def _track_overflow(self, k, ncand):
         over = k.detach() + 8.5 > float(self.ell_width)
@@ -1257,11 +1326,19 @@ class DGG_LearnableK_debug(nn.Module):
                 xp = xp_dual if xp_dual is not None else ops.LinearFn.apply(x, We, be, ops.ACT_LEAKY, 0)
                 cfg["want_bwd"] = ops.backward_will_follow(xp, k)
                 w, idx, val, rs = _DGGWideAdjFn.apply(xp, k, cfg)
-                if writer is not None:
-                    f = w.detach() if (cfg["mode"] == ops.MODE_K_ONLY or "fwd_mode" in cfg) else (w.detach() / val.clamp(min=1e-30))
-                    fs = torch.zeros(x.shape[0], device=x.device).index_add_(0, lay.cnode.long(), f.sum(-1))
-                    writer.add_scalar("values/first_k_std", fs.std(), epoch)
-                    writer.add_scalar("values/first_k_mean", fs.mean(), epoch)
+                self._log_first_k_chunked(writer, epoch, cfg, w, val, lay)
+                return EllAdjacency(idx, w, x.shape[0], rs=rs, k=k.detach(), score=val, owner=self, layout=lay)
+            chunk_checked = lay is not None
+        elif ap_mlp and self._allpairs_mlp_chunked() and not _capturing():
+            # the same for the edge-MLP scorers (args.dgg_allpairs_mlp_rows = "chunked"): every pair is scored, a row keeps its
+            # ceil(k_i + 8.5) + 1 best in chunks of 64 (dgg_allpairs_mlp_topk_wide)
+            lay = ops.chunk_layout(k.detach(), ncols=x.shape[0])          # (one readback: the chunk count sizes the arrays)
+            if lay is not None and lay.wide:
+                mlp, _ = self._edge_mlp_terms(None)
+                cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], layout=lay)
+                w, idx, val, rs = _DGGAllPairsMlpWideAdjFn.apply(x, k, deg, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"],
+                                                                 mlp["w2"], mlp["b2"], cfg)
+                self._log_first_k_chunked(writer, epoch, cfg, w, val, lay)
                 return EllAdjacency(idx, w, x.shape[0], rs=rs, k=k.detach(), score=val, owner=self, layout=lay)
             chunk_checked = lay is not None
         else:

@@ -713,6 +713,60 @@ def allpairs_mlp_topk(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act
     return idx, val, ex
 
 
+APMLP_WIDE_REG_CHUNKS = 8     # chunks of a row that one sweep of dgg_allpairs_mlp_topk_wide settles (MR of dgg_allpairs_mlp_wide.hip); wider
+                              # rows take ceil(maxm / 8) sweeps
+
+
+def allpairs_mlp_topk_wide(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, k, layout, mode=MODE_K_TIMES_EDGE_PROB,
+                           noise_mode=NOISE_NONE, G=None, seed=(0, 0), rows=None, out=None):
+    """allpairs_mlp_topk for rows of ANY width, on chunked rows with the ramp fused (dgg_allpairs_mlp_topk_wide): row i keeps its
+    ceil(k_i + 8.5) + 1 best columns in the chunks of `layout` = chunk_layout(k of these rows, ncols=N)
+    -> idx, val, ex [chunks,64] (ex None for ex_mode 0), w [chunks,64], rs [r1-r0].  mode: MODE_K_TIMES_EDGE_PROB / MODE_K_ONLY /
+    MODE_HARD_ST.  rows = (r0, r1): those rows only (k and layout are theirs; AB, xp, deg stay every node's, G stays [N, N]).
+    out = (idx, val, ex, w, rs): write into these tensors (tests: canaried buffers of any capacity >= layout.chunks; the spare chunks
+    come back empty) instead of fresh ones."""
+    AB, xp, k = _chk(AB), _chk(xp), _chk(k)
+    N, h = xp.shape
+    hw = AB.shape[1] // 2
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    n = max(r1 - r0, 0)
+    assert layout.rows == n and k.shape[0] == n, "allpairs_mlp_topk_wide: k and layout of the rows asked for"
+    if out is None:
+        C_ = layout.chunks
+        idx = torch.empty((C_, 64), device=xp.device, dtype=torch.int32)
+        val = torch.empty((C_, 64), device=xp.device, dtype=torch.float32)
+        ex = torch.empty((C_, 64), device=xp.device, dtype=torch.float32) if ex_mode else None
+        w = torch.empty((C_, 64), device=xp.device, dtype=torch.float32)
+        rs = torch.empty((n,), device=xp.device, dtype=torch.float32)
+    else:
+        idx, val, ex, w, rs = out
+        C_ = idx.shape[0]
+        assert C_ >= layout.chunks
+    ldG = 0
+    if G is not None:
+        G = _chk(G)
+        ldG = G.shape[-1]
+    o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
+    _lib.check(_lib.lib().dgg_allpairs_mlp_topk_wide(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
+                                                     _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act, noise_mode,
+                                                     _ptr(G), ldG, seed[0], seed[1], _ptr(k), mode, layout.maxm, _ptr(layout.cptr), C_,
+                                                     _ptr(idx), _ptr(val), _ptr(ex), _ptr(w), _ptr(rs), _stream()), "allpairs_mlp_topk_wide")
+    return idx, val, ex, w, rs
+
+
+def softk_bwd_chunked(idx, val, k, dw, layout, mode=MODE_K_TIMES_EDGE_PROB):
+    """ramp backward on chunked rows (dgg_softk_bwd_chunked): dw [chunks,64] -> dval [chunks,64] (0 on empty slots), dk [rows]; the
+    rank of an entry is 64 x (its chunk's place in the row) + its lane.  dk is one wavefront's sum per node: deterministic."""
+    idx = _chk(idx, torch.int32)
+    C_ = idx.shape[0]
+    assert C_ >= layout.chunks and tuple(idx.shape) == (C_, 64) and tuple(dw.shape) == (C_, 64)
+    dval = torch.empty((C_, 64), device=idx.device, dtype=torch.float32)
+    dk = torch.empty((layout.rows,), device=idx.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dgg_softk_bwd_chunked(_ptr(idx), _ptr(None if val is None else _chk(val)), _ptr(_chk(k)), _ptr(_chk(dw)), layout.rows,
+                                                _ptr(layout.cptr), C_, mode, _ptr(dval), _ptr(dk), _stream()), "softk_bwd_chunked")
+    return dval, dk
+
+
 def edge_mlp_bwd(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, act=ACT_LEAKY, perturb=False, need_dex=False,
                  rowptr=None, partp=None, w=None, nrec_max=0, rows=None):
     """-> dAB [N,2hw], dpar [5hw+1] = [dwdu|dwdv|dwex|db1|dw2|db2], dex (shape of dval) or None.
@@ -739,6 +793,16 @@ def edge_mlp_bwd(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, ac
                                                      _ptr(o(deg)), _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)),
                                                      _ptr(_chk(w2)), _ptr(_chk(b2)), act, int(perturb), _ptr(partp.ws), partp.ncols, _ptr(dz),
                                                      int(nrec_max), _ptr(dAB), _ptr(dpar), _ptr(dex), _stream()), "edge_mlp_bwd_partp")
+        return dAB, dpar, dex
+    if rowptr is not None:
+        # CSR form: the parameter sums in a fixed order (dgg_edge_mlp_bwd_det) -- dpar has the same bits in every run, and the few hundred
+        # workgroup sums of a cancelling sum such as db2 are added in double instead of by float atomics in arrival order
+        nwg = max(1, min((N + 3) // 4, 1024))
+        ws = torch.empty((nwg * (5 * hw + 2),), device=AB.device, dtype=torch.float32)
+        _lib.check(_lib.lib().dgg_edge_mlp_bwd_det(_ptr(AB), N, hw, 0, N, _ptr(rowptr), _ptr(idx), _ptr(eid), _ptr(_chk(val)), _ptr(_chk(dval)), K,
+                                                   _ptr(o(deg)), _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)),
+                                                   _ptr(_chk(w2)), _ptr(_chk(b2)), act, int(perturb), _ptr(dAB), _ptr(dpar), _ptr(dex), _ptr(ws),
+                                                   ws.numel(), _stream()), "edge_mlp_bwd_det")
         return dAB, dpar, dex
     _lib.check(_lib.lib().dgg_edge_mlp_bwd(_ptr(AB), N, hw, _ptr(rowptr), _ptr(idx), _ptr(eid), _ptr(_chk(val)), _ptr(_chk(dval)), K, _ptr(o(deg)),
                                            _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)),
