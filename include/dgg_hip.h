@@ -556,6 +556,17 @@ int dgg_softk_bwd_chunked(const int32_t *idx, const float *val, const float *k, 
  * (ahat_rows [N,K]: the normalised values).  Reference: autograd of normalize_adj + select_top_k, model.py:1205-1219, dgm.py:1402-1421 */
 int dgg_softk_bwd_rows(const int32_t *idx, const float *val, const float *k, const float *rs, const float *dA, const float *da_cols,
                        const float *ahat_rows, int64_t N, int K, int64_t row0, int mode, float *dval, float *dk, void *stream);
+/* dgg_softk_bwd_rows on the CHUNKED rows of a row shard (modes 0 / 1): idx / val / dA / ahat / dval [ccap,64], k / dk [rows] and
+ * cptr [rows+1] belong to the shard's rows, rs and da_cols have GLOBAL length (row i is node row0 + i; da_cols = the neighbour-side sums
+ * only, summed over the ranks by the caller).  With a = rs^-1/2: row side = rs_i^1/2 sum_r dA_ir ahat_ir over ALL chunks of the row,
+ * d loss / d rs_i = -1/2 rs_i^-3/2 (row side + da_cols[row0 + i]), dw_ir = dA_ir a_i a_j + d loss / d rs_i, then the ramp backward of
+ * dgg_softk_bwd_chunked with rank = 64 (chunk - cptr[i]) + lane.  One wavefront per node, two walks over its chunks, no atomics: dk has
+ * the same bits in every run.  dval is overwritten on all ccap chunks (0 on empty slots, idx < 0, and on the chunks from cptr[rows] on).
+ * rows == 0: returns 0 without a launch.  DGG_ERR_ARG, nothing written: a missing operand (val may be NULL in mode 1), a mode outside
+ * {0, 1}, row0 < 0.  Reference: autograd of normalize_adj + select_top_k over a dense row, model.py:1205-1219, dgm.py:1402-1421 */
+int dgg_softk_bwd_rows_chunked(const int32_t *idx, const float *val, const float *k, const float *rs, const float *dA,
+                               const float *da_cols, const float *ahat, int64_t rows, const int32_t *cptr, int64_t ccap, int64_t row0,
+                               int mode, float *dval, float *dk, void *stream);
 /* score backward to the projected features: dxp [Nglobal,h] += ... (zeroed by caller; fp32 atomics) */
 int dgg_edge_bwd(const float *xp, int64_t N, int h, const int32_t *idx, const float *val, const float *dval, int K,
                  int64_t row0, float t, int perturb, float *dxp, void *stream);

@@ -620,6 +620,61 @@ __global__ __launch_bounds__(WPB * 64) void softk_bwd_chunked_kernel(const int32
     if (lane == 0) dk[i] = skp;
 }
 
+// softk_bwd_kernel with ahat_rows (NORMALISED adjacency, neighbour-side sums in da_cols; modes 0 / 1) on the CHUNKED rows of a row shard:
+// one wavefront per node, two walks over its chunks [cptr[i], cptr[i+1]) -- contiguous 256-byte lines, lane l owns slot l of each.  Walk 1
+// forms the row side rs_i^1/2 sum_r dA_ir ahat_ir over ALL chunks of the row (per-lane fmaf chain in chunk order, then the xor
+// butterfly of softk_bwd_kernel: a one-chunk row sums in that kernel's order); walk 2 applies dw = dA a_i a_j + d loss / d rs_i and the
+// ramp backward with rank = 64 (chunk - cptr[i]) + lane.  rs / da_cols are GLOBAL (row i is node row0 + i).  dk_i is the wavefront's own
+// sum: no atomics, the same bits on every run.  Empty slots get dval = 0 and contribute nothing (their dA / ahat are not trusted); the
+// workgroups beyond the rows zero dval on the spare chunks [cptr[rows], ccap).
+__global__ __launch_bounds__(WPB * 64) void softk_bwd_rows_chunked_kernel(const int32_t *__restrict__ idx, const float *__restrict__ val,
+                                                                         const float *__restrict__ k, const float *__restrict__ rs,
+                                                                         const float *__restrict__ dA, const float *__restrict__ da_cols,
+                                                                         const float *__restrict__ ahat, int64_t rows,
+                                                                         const int32_t *__restrict__ cptr, int64_t ccap, int64_t row0, int mode,
+                                                                         float *__restrict__ dval, float *__restrict__ dk, unsigned nrow_blocks) {
+    const int lane = threadIdx.x & 63;
+    if (blockIdx.x >= nrow_blocks) {
+        const int64_t q = (int64_t)cptr[rows] + (int64_t)(blockIdx.x - nrow_blocks) * WPB + dgg::wave_id();
+        if (q >= 0 && q < ccap) dval[q * 64 + lane] = 0.0f;
+        return;
+    }
+    const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
+    if (i >= rows) return;
+    const int c0 = cptr[i] > 0 ? cptr[i] : 0;
+    const int c1 = (int64_t)cptr[i + 1] < ccap ? cptr[i + 1] : (int)ccap;
+    const float ki = k[i];
+    const float rsi = rs[row0 + i];
+    const float ai = inv_sqrt_c(rsi);
+    float darow = 0.0f;
+    for (int c = c0; c < c1; c++) {
+        const int64_t e = (int64_t)c * 64 + lane;
+        const float g = dA[e], a = ahat[e];
+        darow = idx[e] >= 0 ? fmaf(g, a, darow) : darow;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) darow += __shfl_xor(darow, off, 64);
+    darow *= sqrtf(rsi);
+    const float drs = -0.5f * (da_cols[row0 + i] + darow) * ai / rsi;
+    float skp = 0.0f;
+    for (int c = c0; c < c1; c++) {
+        const int64_t e = (int64_t)c * 64 + lane;
+        const int32_t j = idx[e];
+        const bool live = j >= 0;
+        const float aj = inv_sqrt_c(rs[live ? (int64_t)j : row0 + i]);
+        const float dw = dA[e] * ai * aj + drs;
+        const float v = mode == 0 ? val[e] : 0.0f;              // kernel-uniform branch (val may be NULL in mode 1)
+        const float th = c_tanh((float)(64 * (c - c0) + lane) - ki);
+        const float f = 1.0f - 0.5f * (1.0f + th);
+        const float dfdk = 0.5f * (1.0f - th * th);
+        skp += live ? (mode == 0 ? dw * v * dfdk : dw * dfdk) : 0.0f;
+        dval[e] = (live && mode == 0) ? dw * f : 0.0f;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) skp += __shfl_xor(skp, off, 64);
+    if (lane == 0) dk[i] = skp;
+}
+
 // score backward: dval (wrt the stored score) -> dxp (fp32 atomics; dxp zeroed by caller).  Features on lanes.
 __global__ __launch_bounds__(WPB * 64) void edge_bwd_kernel(const float *__restrict__ xp, int64_t N, int h,
                                                            const int32_t *__restrict__ idx, const float *__restrict__ val,
@@ -1221,6 +1276,23 @@ int dgg_softk_bwd_chunked(const int32_t *idx, const float *val, const float *k, 
     hipLaunchKernelGGL(softk_bwd_chunked_kernel, dim3(nrow_blocks + rows_grid(tail)), dim3(WPB * 64), 0, (hipStream_t)stream, idx, val, k, dw,
                        rows, cptr, ccap, mode, dval, dk, nrow_blocks);
     return dgg_check_launch("softk_bwd_chunked");
+}
+
+int dgg_softk_bwd_rows_chunked(const int32_t *idx, const float *val, const float *k, const float *rs, const float *dA,
+                               const float *da_cols, const float *ahat, int64_t rows, const int32_t *cptr, int64_t ccap, int64_t row0,
+                               int mode, float *dval, float *dk, void *stream) {
+    if (mode != 0 && mode != 1)
+        return dgg_set_error(DGG_ERR_ARG, "softk_bwd_rows_chunked: mode must be 0 (k_times_edge_prob) or 1 (k_only)");
+    if (rows < 0 || row0 < 0 || ccap < 0 || ccap >= ((int64_t)1 << 25))
+        return dgg_set_error(DGG_ERR_ARG, "softk_bwd_rows_chunked: rows >= 0, row0 >= 0, 0 <= ccap < 2^25 chunks");
+    if (rows == 0) return 0;                                    // (an empty shard: its tensors have no data pointer)
+    if (!idx || (mode == 0 && !val) || !k || !rs || !dA || !da_cols || !ahat || !cptr || !dval || !dk)
+        return dgg_set_error(DGG_ERR_ARG, "softk_bwd_rows_chunked: missing operand");
+    const unsigned nrow_blocks = rows_grid(rows);
+    const int64_t tail = ccap > rows ? ccap - rows : 0;         // (every row has at least one chunk, or the capacity is used up)
+    hipLaunchKernelGGL(softk_bwd_rows_chunked_kernel, dim3(nrow_blocks + rows_grid(tail)), dim3(WPB * 64), 0, (hipStream_t)stream, idx, val, k,
+                       rs, dA, da_cols, ahat, rows, cptr, ccap, row0, mode, dval, dk, nrow_blocks);
+    return dgg_check_launch("softk_bwd_rows_chunked");
 }
 
 int dgg_softk_bwd_rows(const int32_t *idx, const float *val, const float *k, const float *rs, const float *dA, const float *da_cols,

@@ -506,7 +506,7 @@ class _FusedDGGConvFn(torch.autograd.Function):
 
 class _FusedDGGMlpConvFn(torch.autograd.Function):
     """_FusedDGGConvFn with an edge-MLP scorer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv; reference dgm.py:1628-1719) on edge-list
-    candidates: the scorer's terms arrive in the per-node / per-edge form of DGG_LearnableK_debug._edge_mlp_terms (sliced from the
+    candidates, or (u-v-deg, u-v-deg-dist, edge_conv; args.dgg_allpairs_mlp_fused = True) on all-pairs candidates: the scorer's terms arrive in the per-node / per-edge form of DGG_LearnableK_debug._edge_mlp_terms (sliced from the
     reference's parameters by differentiable torch ops outside this node) and get their gradients from the same backward."""
 
     @staticmethod
@@ -708,7 +708,9 @@ class DGG_LearnableK_debug(nn.Module):
         (_FusedDGGConvFn) -> (Z, unnormalised EllAdjacency, DETACHED: its values carry no autograd edge -- the loss of the
         reference's training scripts reads the class scores only, train_small_graphs.py:226-230), or None when this configuration
         is outside the fused step (the caller then runs the modules one after the other): scorer u-v-dist (any candidates) or an
-        edge-MLP scorer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv, A_uv; edge-list candidates), k-net "x", soft
+        edge-MLP scorer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv, A_uv on edge-list candidates; u-v-deg, u-v-deg-dist, edge_conv on
+        all-pairs candidates as an opt-in, args.dgg_allpairs_mlp_fused = True -- on the 64-rank list or, with args.dgg_allpairs_mlp_rows =
+        "chunked", on chunked rows), k-net "x", soft
         k_times_edge_prob / k_only output, widths the partitioned backward covers, rows that fit the ELL width.
         want_norm: additionally return the NORMALISED adjacency as a differentiable EllAdjacency for the layers that read the same
         graph after this one (GCN_DGG's second layer): its gradient flows back into the generator through the same node.
@@ -729,8 +731,9 @@ class DGG_LearnableK_debug(nn.Module):
         wide_state = None
         if isinstance(in_adj, AllPairs):
             cand, deg, rowptr = None, in_adj.prior_degree, None
-            if self.__dict__.get("_ap_wide", {}).get("on") or (getattr(a, "dgg_wide_rows", "auto") == "csr" and
-                                                               N <= int(getattr(a, "dgg_allpairs_csr_max", 8192))):
+            # (args.dgg_wide_rows is u-v-dist's: the edge-MLP scorers have args.dgg_allpairs_mlp_rows, and no CSR form on all pairs)
+            if not mlp_mode and (self.__dict__.get("_ap_wide", {}).get("on") or (getattr(a, "dgg_wide_rows", "auto") == "csr" and
+                                                                                 N <= int(getattr(a, "dgg_allpairs_csr_max", 8192)))):
                 return None                                   # (policy "csr": every column ranked, the modules' CSR form)
         else:
             if isinstance(in_adj, EllAdjacency):
@@ -767,7 +770,17 @@ class DGG_LearnableK_debug(nn.Module):
         mlp_mode = self.edge_prob_net_mode in _EDGE_MLP_FUSED
         clauses = (
             ("scorer outside u-v-dist / the edge-MLP family", self.edge_prob_net_mode != "u-v-dist" and not mlp_mode),
-            ("edge-MLP scorer on all-pairs candidates", mlp_mode and isinstance(in_adj, AllPairs)),
+            # an edge-MLP scorer on all-pairs candidates enters the fused layer (and ShardedGCN_DGG) as an OPT-IN,
+            # args.dgg_allpairs_mlp_fused = True: without it the forward keeps the separate modules it has always taken -- their bits,
+            # their autograd edges (a differentiable unnorm_adj) and this clause in fused_fallback
+            ("edge-MLP scorer on all-pairs candidates",
+             mlp_mode and isinstance(in_adj, AllPairs) and not getattr(a, "dgg_allpairs_mlp_fused", False)),
+            # (all-pairs candidates have no stored values: u-v-A_uv / A_uv raise in forward(), where the separate modules send them)
+            ("edge-MLP scorer on all-pairs candidates that reads the stored values of in_adj (u-v-A_uv / A_uv)",
+             mlp_mode and isinstance(in_adj, AllPairs) and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS),
+            # (dgg_allpairs_mlp_topk is built for these widths; edge_conv's hidden width is latent_dim / 2)
+            ("edge-MLP scorer on all-pairs candidates: latent / hidden width outside {16, 32, 64, 128} (edge_conv: latent from 32)",
+             mlp_mode and isinstance(in_adj, AllPairs) and (h not in (16, 32, 64, 128) or (self.edge_prob_net_mode == "edge_conv" and h == 16))),
             ("k-net mode other than 'x'", self.k_net_mode != "x"),
             ("k-select mode other than k_times_edge_prob / k_only", self.k_select_mode not in ("k_times_edge_prob", "k_only")),
             ("dgg_hard", bool(self.hard)),
@@ -785,9 +798,11 @@ class DGG_LearnableK_debug(nn.Module):
         return next((why for why, hit in clauses if hit), None)
 
     def _fused_scorer(self, in_adj):
-        """the edge-MLP scorer's parameters and per-edge inputs for the fused node, in the CSR order of the candidates -> (mlp, static)"""
+        """the edge-MLP scorer's parameters and per-edge inputs for the fused node, in the CSR order of the candidates -> (mlp, static).
+        All-pairs candidates (the scorers of _EDGE_MLP_ALLPAIRS) have no per-edge inputs and no pattern is read: erow = ex_in = None."""
         h = self.latent_dim
-        avals = _cached("values_f32", in_adj, lambda: in_adj.coalesce().values().to(torch.float32).contiguous())
+        all_pairs = isinstance(in_adj, AllPairs)
+        avals = None if all_pairs else _cached("values_f32", in_adj, lambda: in_adj.coalesce().values().to(torch.float32).contiguous())
         if self.edge_prob_net_mode in ("edge_conv", "A_uv"):
             mlp, ex_in = self._edge_mlp_terms(avals)
             packed = None
@@ -801,20 +816,29 @@ class DGG_LearnableK_debug(nn.Module):
                        b2=self.edge_encode[2].bias, act=ops.ACT_LEAKY, ex_mode={"u-v-deg": 0, "u-v-A_uv": 1, "u-v-deg-dist": 2}[self.edge_prob_net_mode],
                        t_ex=-1.0 if self.edge_prob_net_mode == "u-v-deg-dist" else 0.0)
             ex_in = avals if self.edge_prob_net_mode == "u-v-A_uv" else None
-        return mlp, dict(erow=csr_pattern(in_adj)[2], ex_in=ex_in, ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], packed=packed)
+        return mlp, dict(erow=None if all_pairs else csr_pattern(in_adj)[2], ex_in=ex_in, ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], packed=packed)
 
     def _fused_configure(self, layer, x, cand, wide_state, mlp_mode):
         """sets the engine up for this forward: noise generator, selection mode, what rows wider than 64 ranks do, device flags
         -> (noise_mode, chunk_active = this forward reads its chunk layout back)"""
         a, N = self.args, x.shape[0]
         noise_mode, _, seed = self._noise_cfg()
-        if cand is None and noise_mode == ops.NOISE_RANKED:
+        ap_mlp = cand is None and mlp_mode                    # edge-MLP scorer on all-pairs candidates: every pair is scored, as on edge lists
+        if cand is None and noise_mode == ops.NOISE_RANKED and not ap_mlp:
             noise_mode = self._asym_generator_now(x, seed)
-        elif cand is not None:
+        elif cand is not None or ap_mlp:
             noise_mode = {ops.NOISE_RANKED: ops.NOISE_HASH, ops.NOISE_RANKED_SYM: ops.NOISE_HASH_SYM}.get(noise_mode, noise_mode)
         mode = ops.MODE_K_TIMES_EDGE_PROB if self.k_select_mode == "k_times_edge_prob" else ops.MODE_K_ONLY
         layer.cand, layer.noise_mode, layer.seed, layer.mode, layer.scorer = cand, noise_mode, seed, mode, None
         layer.sym_fallback, layer.sym_hash = getattr(a, "dgg_sym_generator", "auto") != "ranked", False
+        if ap_mlp:
+            # none of the ranked generators' pilots and fallbacks applies; rows wider than the list under the scorers' own opt-in
+            # (args.dgg_allpairs_mlp_rows = "chunked"; a hipGraph capture keeps the list and its enforced bound: nothing can be read back)
+            layer.sym_fallback, layer.force_chunked, layer.tight_bound = False, False, "off"
+            layer.x_grad = bool(x.requires_grad)
+            chunked = self._allpairs_mlp_chunked() and not _capturing()
+            layer.wide_rows, layer.wide_cap = ("auto" if chunked else "off"), None
+            return noise_mode, chunked
         # the module fell back from the ranked symmetric generator on THIS data (spread latents): the hash noise's forwards take the
         # chunked rows' per-row front end, whatever the learned degrees (parallel.py, force_chunked)
         # ... and so do forwards under a per-pair hash generator the CALLER chose (args.dgg_sym_generator / dgg_asym_generator = "hash")
@@ -862,13 +886,13 @@ class DGG_LearnableK_debug(nn.Module):
                 self._overflow_scratch.zero_()
             return None
         lay = st.get("layout")
-        if cand is None and lay is None and not chunk_active and self._allpairs_wide(N, k):
+        if cand is None and not mlp_mode and lay is None and not chunk_active and self._allpairs_wide(N, k):
             return None                                       # learned degrees beyond the list: the modules' CSR form (every column ranked)
         if cand is None and lay is None and not chunk_active:
             self._track_overflow(k, None)
         elif cand is None and layer.wide_cap is not None:     # fixed capacity (capture): overflow flags in layer.wide_sticky (check_ell_bound)
             pass
-        elif mlp_mode:
+        elif mlp_mode and cand is not None:
             ent = self.__dict__.get("_wide_cache", {}).get(id(in_adj))
             if not (ent is not None and ent[0]() is in_adj and ent[1] <= self.ell_width):     # (no row can outgrow the list otherwise)
                 self._track_overflow(k, self._row_lens(rowptr, layer))

@@ -15,7 +15,15 @@ Edge-list candidates (a sparse in_adj, the reference's own configuration: dgm.py
 and the edge-MLP scorers of the fused layer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv, A_uv), under no / hash / symmetric hash noise:
 every rank scores its own rows' candidates through the row-range kernels, and the scorer's gradients are summed with the layer's.
 
-Rows wider than the 64-rank list whose learned degree needs more ranks than that leave the fused layer for the CSR form
+All-pairs candidates run with the u-v-dist scorer and with the edge-MLP scorers that read the end nodes and their prior degrees only
+(u-v-deg, the reference training script's default, u-v-deg-dist, edge_conv -- an opt-in, args.dgg_allpairs_mlp_fused = True, as for the
+fused layer on one GPU; without it the wrapper raises as before; no / hash / symmetric hash noise -- the ranked generators give
+way to the per-pair hash of the same law, as on one GPU): every rank scores all N columns of its own rows through the row range of
+dgg_allpairs_mlp_topk, or of dgg_allpairs_mlp_topk_wide on chunked rows under args.dgg_allpairs_mlp_rows = "chunked", and the adjacency
+returned is the rank's rows with global columns (`layout` set for chunked rows).  The N^2 scoring is row-parallel, so this is the
+configuration a row shard divides best; no run on several GPUs has been timed.
+
+Edge-list rows wider than the 64-rank list whose learned degree needs more ranks than that leave the fused layer for the CSR form
 (DGG_LearnableK_debug._csr_soft_adjacency -> CsrAdjacency.normalize -> GCNConv on a CsrAdjacency), on one GPU and, as an OPT-IN, on a row
 shard: args.dgg_wide_rows = "csr" (the CSR form from the first forward) or "csr_auto" (the fused layer until the collective wide-row flag
 first fires, the CSR form for that forward -- recomputed -- and every later one on that graph).  Under the default "auto" such a forward
@@ -311,7 +319,8 @@ class ShardedGCN_DGG(nn.Module):
         policy = getattr(a, "dgg_wide_rows", "auto")
         if policy not in ("auto", "chunked"):
             raise NotImplementedError(f"ShardedGCN_DGG: args.dgg_wide_rows = {policy!r} (rows wider than the list need the chunked form)")
-        if self.world > 1 and getattr(a, "dgg_sym_generator", "ranked") == "auto":
+        # (the edge-MLP scorers score every pair under the per-pair hash generators: no ranked generator, nothing to switch)
+        if self.world > 1 and getattr(a, "dgg_sym_generator", "ranked") == "auto" and dgg.edge_prob_net_mode == "u-v-dist":
             raise NotImplementedError("ShardedGCN_DGG: args.dgg_sym_generator = 'auto' switches generators from one rank's rows; "
                                       "choose 'ranked' or 'hash' on several ranks")
         why = dgg._fused_outside(x, in_adj, m.conv1.W)

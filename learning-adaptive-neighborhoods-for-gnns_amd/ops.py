@@ -767,6 +767,27 @@ def softk_bwd_chunked(idx, val, k, dw, layout, mode=MODE_K_TIMES_EDGE_PROB):
     return dval, dk
 
 
+def softk_bwd_rows_chunked(idx, val, k, rs, dA, da_cols, ahat, layout, row0=0, mode=MODE_K_TIMES_EDGE_PROB, out=None):
+    """ramp + normalisation backward on the chunked rows of a row shard (dgg_softk_bwd_rows_chunked): dA [chunks,64] = cotangent of the
+    NORMALISED values ahat, da_cols [N] = the neighbour-side sums of d loss / d (rs^-1/2) (conv_bwd_cols_p; summed over the ranks), rs [N]
+    every node's row sums, row i = node row0 + i -> dval [chunks,64] (0 on empty slots and spare chunks), dk [rows].  The row side of
+    the normalisation backward is formed inside, over all chunks of a row; dk is one wavefront's sum per node: deterministic.
+    out = (dval, dk): write into these tensors (tests: canaried buffers)."""
+    idx = _chk(idx, torch.int32)
+    C_ = idx.shape[0]
+    assert C_ >= layout.chunks and tuple(idx.shape) == (C_, 64) and tuple(dA.shape) == (C_, 64) and tuple(ahat.shape) == (C_, 64)
+    assert k.shape[0] == layout.rows and rs.shape[0] >= int(row0) + layout.rows and da_cols.shape[0] == rs.shape[0]
+    if out is None:
+        dval = torch.empty((C_, 64), device=idx.device, dtype=torch.float32)
+        dk = torch.empty((layout.rows,), device=idx.device, dtype=torch.float32)
+    else:
+        dval, dk = out
+    _lib.check(_lib.lib().dgg_softk_bwd_rows_chunked(_ptr(idx), _ptr(None if val is None else _chk(val)), _ptr(_chk(k)), _ptr(_chk(rs)),
+                                                     _ptr(_chk(dA)), _ptr(_chk(da_cols)), _ptr(_chk(ahat)), layout.rows, _ptr(layout.cptr), C_,
+                                                     int(row0), mode, _ptr(dval), _ptr(dk), _stream()), "softk_bwd_rows_chunked")
+    return dval, dk
+
+
 def edge_mlp_bwd(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, b2, act=ACT_LEAKY, perturb=False, need_dex=False,
                  rowptr=None, partp=None, w=None, nrec_max=0, rows=None):
     """-> dAB [N,2hw], dpar [5hw+1] = [dwdu|dwdv|dwex|db1|dw2|db2], dex (shape of dval) or None.
@@ -832,6 +853,16 @@ def _edge_mlp_bwd_rows(AB, idx, eid, val, dval, deg, ex, wdu, wdv, wex, b1, w2, 
                                                           K, _ptr(o(deg)), _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)),
                                                           _ptr(_chk(w2)), _ptr(_chk(b2)), act, int(perturb), _ptr(partp.ws), _ptr(dz), int(nrec_max),
                                                           _ptr(dAB), _ptr(dpar), _ptr(dex), _stream()), "edge_mlp_bwd_partp_rows")
+        return dAB, dpar, dex
+    if rowptr is not None:
+        # CSR form of a row shard: the parameter sums in a fixed order, as edge_mlp_bwd's CSR form has them on the whole graph
+        # (dgg_edge_mlp_bwd_det) -- a shard's dpar has the same bits in every run
+        nwg = max(1, min((n + 3) // 4, 1024))
+        ws = torch.empty((nwg * (5 * hw + 2),), device=AB.device, dtype=torch.float32)
+        _lib.check(_lib.lib().dgg_edge_mlp_bwd_det(_ptr(AB), N, hw, r0, r1, _ptr(rowptr), _ptr(idx), _ptr(eid), _ptr(_chk(val)), _ptr(_chk(dval)), K,
+                                                   _ptr(o(deg)), _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)),
+                                                   _ptr(_chk(w2)), _ptr(_chk(b2)), act, int(perturb), _ptr(dAB), _ptr(dpar), _ptr(dex), _ptr(ws),
+                                                   ws.numel(), _stream()), "edge_mlp_bwd_det")
         return dAB, dpar, dex
     _lib.check(_lib.lib().dgg_edge_mlp_bwd_rows(_ptr(AB), N, hw, r0, r1, _ptr(rowptr), _ptr(idx), _ptr(eid), _ptr(_chk(val)), _ptr(_chk(dval)), K,
                                                 _ptr(o(deg)), _ptr(o(ex)), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)),

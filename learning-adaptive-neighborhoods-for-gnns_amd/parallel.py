@@ -106,7 +106,7 @@ def _all_gather_rows(t_local, N, per, group, bufs=None, key=None):
 class KernelContract:
     """What ShardedDGGConv may call on its kernel namespace BEYOND the baseline entries (linear_fwd / linear_bwd, degree_stats,
     knet_x_fwd / knet_x_bwd, allpairs_topk, edgelist_topk, edgelist_topk_p, edge_mlp_fwd / edge_mlp_bwd, softk_fwd / softk_bwd,
-    normalize_fwd, spmm_fwd / spmm_bwd, act_bwd, norm_bwd_da, edge_bwd), written down once.  Every optional entry answers None --
+    normalize_fwd, spmm_fwd / spmm_bwd, act_bwd, norm_bwd_da, edge_bwd, csr_uvdist_bwd), written down once.  Every optional entry answers None --
     what dgg_amd.ops answers for "does not cover this shape" -- and every optional flag is off, so the engine calls them
     unconditionally and takes its fallback where it takes the shape fallback.  dgg_amd.ops provides every name with these parameter
     names (tests/test_kernel_contract.py); a test stand-in inherits from this class and defines the baseline entries only."""
@@ -141,6 +141,18 @@ class KernelContract:
         return None
 
     def chunk_layout(self, k, maxm=None, ccap=None, ncols=None, sticky=None):
+        return None
+
+    # the edge-MLP scorer on ALL-PAIRS candidates: scorer + perturbation + top-K of every pair in one kernel, on the 64-rank list and on
+    # chunked rows, and the ramp + normalisation backward of the chunked rows of a row shard.  An engine whose scorer needs them raises
+    # when the namespace answers None: every pair has to be scored, and there is no other evaluator to fall back to
+    def allpairs_mlp_topk(self, AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, K, noise_mode, G, seed, rows=None):
+        return None
+
+    def allpairs_mlp_topk_wide(self, AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, k, layout, mode, noise_mode, G, seed, rows=None):
+        return None
+
+    def softk_bwd_rows_chunked(self, idx, val, k, rs, dA, da_cols, ahat, layout, row0=0, mode=0):
         return None
 
     def rowmin_logp_bound(self, xp, t, rows=None):
@@ -214,10 +226,14 @@ def edge_mlp_score_bwd(kern, sc, xp, AB, idx, eid, val, dval, sdeg, ex, perturb,
 
 
 class ShardedDGGConv:
-    """One DGG (all-pairs or edge-list candidates; u-v-dist or, on edge lists, an edge-MLP scorer / x / k_times_edge_prob) + normalise +
-    GCNConv layer, forward and backward, on a row shard.  Parameters are a dict with the reference's names (dgm.py:1097-1143, model.py:583).
-    Edge-list candidates on several ranks need replicated features (x_full): every rank projects xp (and the edge-MLP scorer's AB) for all
-    N nodes, scores its own rows' candidates and sums the scorer's gradients with the layer's in one all-reduce."""
+    """One DGG (all-pairs or edge-list candidates; u-v-dist or an edge-MLP scorer / x / k_times_edge_prob) + normalise + GCNConv layer,
+    forward and backward, on a row shard.  Parameters are a dict with the reference's names (dgm.py:1097-1143, model.py:583).
+    Edge-list candidates, and an edge-MLP scorer on any candidates, need replicated features (x_full) on several ranks: every rank
+    projects xp (and the edge-MLP scorer's AB) for all N nodes, scores its own rows' candidates and sums the scorer's gradients with the
+    layer's in one all-reduce.
+    An edge-MLP scorer on ALL-PAIRS candidates (u-v-deg / u-v-deg-dist / edge_conv: they read the two end nodes and their prior degrees
+    only) scores all N columns of the rank's rows in one kernel (allpairs_mlp_topk; chunked rows under wide_rows: allpairs_mlp_topk_wide)
+    under no / hash / symmetric hash noise keyed on the global pair; DESIGN.md has the step's kernel sequence."""
 
     PARAM_KEYS = ("We", "be", "Wk", "bk", "W1", "b1", "Wmu", "bmu", "Wp", "bp", "Wc")
 
@@ -236,10 +252,11 @@ class ShardedDGGConv:
         # launch-bound (Pubmed: 0.29 ms fused on one GPU) and gains nothing from a shard; where larger edge lists stop being
         # launch-bound has not been measured.
         self.cand = cand
-        # scorer (edge-list candidates only): None = exp(t ||xp_i - xp_j||) (u-v-dist), or a dict with the edge-MLP scorer's terms in
-        # the per-node / per-edge form of dgg_edge_mlp_fwd (reference dgm.py:1628-1719): Wcat [2hw,h], wdu / wdv / wex [hw] or None,
-        # b1 [hw], w2 [hw], b2 [1], erow int32 [E], ex_in [E] or None, ex_mode, t_ex, act.  backward() then also returns
-        # g["scorer"] = {Wcat, wdu, wdv, wex, b1, w2, b2} (the rest of the step is the same)
+        # scorer: None = exp(t ||xp_i - xp_j||) (u-v-dist), or a dict with the edge-MLP scorer's terms in the per-node / per-edge form
+        # of dgg_edge_mlp_fwd (reference dgm.py:1628-1719): Wcat [2hw,h], wdu / wdv / wex [hw] or None, b1 [hw], w2 [hw], b2 [1],
+        # ex_mode, t_ex, act and, on edge-list candidates, erow int32 [E] and ex_in [E] or None (all-pairs candidates have no per-edge
+        # inputs: ex_mode 0 or 2, hw and h in {16, 32, 64, 128}).  backward() then also returns g["scorer"] = {Wcat, wdu, wdv, wex, b1,
+        # w2, b2} (the rest of the step is the same)
         self.scorer = None
         assert cand is None or noise_mode in (0, 2, 3), "edge-list candidates: noise_mode none / hash / symmetric hash"
         assert x_full is None or not x_grad, "replicated features are data: they cannot take a gradient"
@@ -503,6 +520,8 @@ class ShardedDGGConv:
         s["layout"] = None
         if self.cand is not None:
             return self._search_edge_list(s, deg_full)
+        if self.scorer is not None:
+            return self._search_allpairs_mlp(s, deg_full)
         if self.noise_mode == 4 and self.K == 64 and xp.shape[1] in (8, 16, 32, 64, 128):
             # ranked noise: the ramp is applied inside the search kernel, while the settled list is still in registers
             s["layout"] = lay = self._chunk_layout(k) if xp.shape[1] in (16, 32, 64, 128) else None
@@ -562,6 +581,41 @@ class ShardedDGGConv:
         if got is not None:                         # search + ramp in one launch
             return got
         idx, val = kern.edgelist_topk(xp, rowptr, col, self.K, self.t, self.noise_mode, None, self.seed, **rk)
+        return (idx, val) + tuple(kern.softk_fwd(idx, val, k, self.mode))
+
+    MLP_NOISE = {0: 0, 2: 2, 3: 3, 4: 2, 5: 3}       # noise_mode -> the generator an edge-MLP scorer's all-pairs rows are evaluated under:
+                                                     # every pair is scored, so the ranked generators (an early-stopping search) give way
+                                                     # to the per-pair hash of the same law, as in the separate modules
+
+    def _search_allpairs_mlp(self, s, deg_full):
+        """_search with an edge-MLP scorer on all-pairs candidates: AB for all N nodes, then scorer + perturbation + top-K of the rank's
+        rows against all N columns in one kernel.  Writes s: AB, sdeg, ex (per slot, flat), eid (the slot index; None on chunked rows,
+        whose backward runs in CSR form on the flattened chunks), layout."""
+        kern, xp, k, sc = self.kern, s["xp"], s["k"], self.scorer
+        assert self.world == 1 or self.x_full is not None, "an edge-MLP scorer on several ranks: replicated features (x_full)"
+        assert self.noise_mode in self.MLP_NOISE, "edge-MLP scorer on all-pairs candidates: counter-based noise or none"
+        nm = self.MLP_NOISE[self.noise_mode]
+        rows = (self.r0, self.r1)
+        s["AB"] = AB = kern.linear_fwd(xp, sc["Wcat"], None, 0, 0)
+        s["sdeg"] = sdeg = deg_full if sc["wdu"] is not None else None
+        terms = (AB, xp, sdeg, sc["ex_mode"], sc["t_ex"], sc["wdu"], sc["wdv"], sc["wex"], sc["b1"], sc["w2"], sc["b2"], sc["act"])
+        s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)) else None
+        if lay is not None:                         # rows wider than 64 ranks: ceil(k_i + 8.5) + 1 ranks of every row, the ramp fused
+            got = kern.allpairs_mlp_topk_wide(*terms, k, lay, self.mode, nm, None, self.seed, rows=rows)
+            if got is None:
+                raise NotImplementedError("ShardedDGGConv: the kernel namespace has no allpairs_mlp_topk_wide (edge-MLP scorer, chunked rows)")
+            idx, val, ex, w, rs_local = got
+            s["ex"], s["eid"] = (None if ex is None else ex.reshape(-1)), None
+            return idx, val, w, rs_local
+        got = kern.allpairs_mlp_topk(*terms, self.K, nm, None, self.seed, rows=rows)
+        if got is None:
+            raise NotImplementedError("ShardedDGGConv: the kernel namespace has no allpairs_mlp_topk (edge-MLP scorer on all-pairs candidates)")
+        idx, val, ex = got
+        s["ex"] = None if ex is None else ex.reshape(-1)
+        eid = self.bufs.get("eid")                  # (an entry's extra is at its slot: the same arange every step)
+        if eid is None or eid.shape != idx.shape or eid.device != idx.device:
+            eid = self.bufs["eid"] = torch.arange(idx.numel(), device=idx.device, dtype=torch.int32).view(idx.shape)
+        s["eid"] = eid
         return (idx, val) + tuple(kern.softk_fwd(idx, val, k, self.mode))
 
     def _gather_row_sums(self, rs_local):
@@ -752,17 +806,43 @@ class ShardedDGGConv:
         """score backward of the edge-MLP scorer: ramp + normalisation backward by rows, then edge_mlp_score_bwd on the selected
         edges -> dxp, dk; writes g["scorer"].  da [N]: d loss / d (rs^-1/2), both sides (dgg_norm_bwd_da), or with ahat_rows the
         neighbour-side sums (the row side is then formed inside the row kernel, dgg_softk_bwd_rows).  Reads s: idx, val, k, rs, xp, AB,
-        eid, sdeg, ex and, for the payload form of the MLP's backward, partp, w, ncand."""
+        eid, sdeg, ex, layout and, for the payload form of the MLP's backward (edge-list candidates), partp, w, ncand."""
         kern, s, sc = self.kern, self.saved, self.scorer
+        kw = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
+        if s["layout"] is not None:
+            return self._scorer_backward_chunked(g, dA, da, ahat_rows, kw)
         akw = {} if ahat_rows is None else {"ahat_rows": ahat_rows}
         dval, dk = kern.softk_bwd(s["idx"], s["val"], s["k"], dA, s["rs"], da, self.r0, self.mode, True, **akw)
-        kw = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
+        # (all-pairs candidates keep the MLP backward's atomic form: the payload form sizes its scratch by the number of candidate
+        #  edges, which is rows x N there -- and the separate modules run the atomic form too)
         if s["partp"] is not None and self.cand is not None and kern.EMLP_BWD_PARTP:
             kw.update(partp=s["partp"], w=s["w"], nrec_max=s["ncand"])       # (a selected entry is one of the rows' candidate edges)
         dxp, dex, g["scorer"] = edge_mlp_score_bwd(kern, sc, s["xp"], s["AB"], s["idx"], s["eid"], s["val"], dval, s["sdeg"], s["ex"],
                                                    self.noise_mode != 0, **kw)
         if sc["ex_mode"] == 2:                              # exp(t ||xp_u - xp_v||) as an edge feature also depends on the projection
             dxp = dxp + kern.edge_bwd(s["xp"], s["idx"], s["val"], dex, self.r0, sc["t_ex"], False)
+        return dxp, dk
+
+    def _scorer_backward_chunked(self, g, dA, da, ahat_rows, kw):
+        """_scorer_backward on chunked rows (all-pairs candidates): ramp + normalisation backward by node over the row's chunks
+        (softk_bwd_rows_chunked; da = the neighbour-side sums), then the MLP's backward in its CSR form on the flattened chunks -- row i's
+        entries are [64 cptr[i], 64 cptr[i+1]), empty slots carry idx = -1 and are skipped; parameter sums in a fixed order -- and the
+        distance term of u-v-deg-dist through csr_uvdist_bwd on the same pattern.  kw: rows= of a row shard."""
+        kern, s, sc = self.kern, self.saved, self.scorer
+        lay = s["layout"]
+        assert ahat_rows is not None, "chunked rows run on the payload partition"
+        got = kern.softk_bwd_rows_chunked(s["idx"], s["val"], s["k"], s["rs"], dA, da, ahat_rows, lay, self.r0, self.mode)
+        if got is None:
+            raise NotImplementedError("ShardedDGGConv: the kernel namespace has no softk_bwd_rows_chunked (edge-MLP scorer, chunked rows)")
+        dval, dk = got
+        rowptr = lay.cptr.to(torch.int64) * 64
+        col = s["idx"].reshape(-1)
+        dxp, dex, g["scorer"] = edge_mlp_score_bwd(kern, sc, s["xp"], s["AB"], col, None, s["val"].reshape(-1), dval.reshape(-1), s["sdeg"],
+                                                   s["ex"], self.noise_mode != 0, rowptr=rowptr, **kw)
+        if sc["ex_mode"] == 2:
+            # (empty slots: ex = 0 from the forward and dex = 0 from the MLP backward's CSR form, so csr_uvdist_bwd skips them before it
+            #  reads the column; the clamp only keeps a column it never uses inside the graph)
+            dxp = dxp + kern.csr_uvdist_bwd(s["xp"], rowptr, col.clamp(min=0), s["ex"], dex, sc["t_ex"], **kw)
         return dxp, dk
 
     def _premask(self):
