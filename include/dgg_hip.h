@@ -334,6 +334,31 @@ int dgg_allpairs_mlp_topk_wide(const float *AB, const float *xp, int64_t N, int 
                                const float *w2, const float *b2, int act, int noise_mode, const float *G, int64_t ldG, uint32_t s0,
                                uint32_t s1, const float *k, int mode, int maxm, const int32_t *cptr, int64_t ccap, int32_t *idx,
                                float *val, float *ex_out, float *w, float *rs, void *stream);
+/* dgg_allpairs_mlp_topk with ex_mode 1: all-pairs candidates scored against a sparse PRIOR graph.  The per-edge extra of pair (i, j) is
+ * the prior's stored value a_ij, 0.0f where the prior stores nothing -- the scorer u-v-A_uv (dgm.py:1628-1644), perturbed (dgm.py:
+ * 1211-1229) and sorted (dgm.py:1404), on the complete in_adj whose stored values are the prior's, zero for non-edges.  Same bits as
+ * dgg_edge_mlp_fwd (ex_mode 1, ex_in = the prior's dense values) + dgg_edgelist_topk_p on the complete pattern.  The prior is CSR:
+ * prior_rowptr [N+1], prior_col [nnz] int32, prior_val [nnz]; they are the WHOLE graph's also when rows [row0, row1) are asked for.
+ * INPUT CONTRACT: the columns of a row are STRICTLY ASCENDING (a coalesced COO in CSR form) and in [0, N); a stored value of
+ * exactly 0 means the same as an absent entry.  Every other argument as dgg_allpairs_mlp_topk: deg (nullable) adds the degree term,
+ * act 0 / 1, wex [hw] is required; ex_out (nullable) [row1-row0, K] = the prior value of (i, idx) for every kept entry, 0.0f for
+ * non-edges and empty slots -- the per-entry extra dgg_edge_mlp_bwd reads.
+ * DGG_ERR_UNSUPPORTED and nothing written: hw or h outside {16, 32, 64, 128}, K > 64, ex_mode other than 1, DGG_NOISE_RANKED /
+ * RANKED_SYM.  DGG_ERR_ARG and nothing written: a NULL CSR array, and the rest as dgg_allpairs_mlp_topk. */
+int dgg_allpairs_mlp_topk_prior(const float *AB, const float *xp, int64_t N, int h, int hw, int64_t row0, int64_t row1, const float *deg,
+                                int ex_mode, float t_ex, const float *wdu, const float *wdv, const float *wex, const float *b1,
+                                const float *w2, const float *b2, int act, int noise_mode, const float *G, int64_t ldG, uint32_t s0,
+                                uint32_t s1, int K, int32_t *idx, float *val, float *ex_out, const int64_t *prior_rowptr,
+                                const int32_t *prior_col, const float *prior_val, void *stream);
+/* dgg_allpairs_mlp_topk_wide with the prior extra of dgg_allpairs_mlp_topk_prior (dgm.py:1628-1644, 1211-1229, 1404 on chunked rows):
+ * same prior arrays and input contract, same outputs and refusals as dgg_allpairs_mlp_topk_wide with ex_mode 1 required.  Every
+ * continuation pass sweeps the columns again and walks each open row's prior entries again from the row's start. */
+int dgg_allpairs_mlp_topk_wide_prior(const float *AB, const float *xp, int64_t N, int h, int hw, int64_t row0, int64_t row1,
+                                     const float *deg, int ex_mode, float t_ex, const float *wdu, const float *wdv, const float *wex,
+                                     const float *b1, const float *w2, const float *b2, int act, int noise_mode, const float *G, int64_t ldG,
+                                     uint32_t s0, uint32_t s1, const float *k, int mode, int maxm, const int32_t *cptr, int64_t ccap,
+                                     int32_t *idx, float *val, float *ex_out, float *w, float *rs, const int64_t *prior_rowptr,
+                                     const int32_t *prior_col, const float *prior_val, void *stream);
 /* autograd of dgg_edge_mlp_fwd for the selected entries: dval (wrt the stored score) -> dAB [N,2*hw] and
  * dpar [5*hw+1] = [dwdu | dwdv | dwex | db1 | dw2 | db2] (both ACCUMULATED into: caller zeroes), dex [N,K] (nullable,
  * overwritten; gradient wrt the per-edge extra).  ex [E] as written by the forward (nullable when ex_mode was 0). */

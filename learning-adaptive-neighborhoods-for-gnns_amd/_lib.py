@@ -64,6 +64,10 @@ PROTOTYPES = {
                               _i32, _vp, _vp, _vp, _vp],
     "dgg_allpairs_mlp_topk_wide": [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _u32,
                                    _u32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dgg_allpairs_mlp_topk_prior": [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _u32,
+                                    _u32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dgg_allpairs_mlp_topk_wide_prior": [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64,
+                                         _u32, _u32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dgg_edgelist_topk_p": [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _u32, _u32, _i32, _vp, _vp, _vp, _vp],
     "dgg_edgelist_topk_p_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _i64, _u32, _u32, _i32, _vp, _vp, _vp, _vp],
     "dgg_edge_mlp_bwd": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],

@@ -12,13 +12,58 @@ from . import ops
 
 class AllPairs:
     """Candidate set = every ordered pair (the reference equivalent is a complete in_adj whose row sums are the
-    prior degrees): carries the prior-degree vector read by the k-net (dgm.py:1568)."""
+    prior degrees): carries the prior-degree vector read by the k-net (dgm.py:1568).
 
-    def __init__(self, prior_degree):
+    prior (optional): the input graph itself, a sparse COO [N, N] tensor (a dense one is converted once) -- the reference equivalent
+    is then the complete in_adj whose stored values are the prior's, zero for non-edges, so what reads the graph (the scorer
+    u-v-A_uv, dgm.py:1628-1644; the k-net gcn-x-deg, dgm.py:1528-1540) runs on all-pairs candidates: the generator may pick edges
+    outside the graph and still sees, for every pair, whether the graph has it.  A stored value of exactly 0 means the same as an
+    absent entry.  The prior is coalesced here (duplicates summed) and kept in CSR form on the object (prior_csr()), and it is used AS
+    GIVEN: the models pass an AllPairs through unchanged, without adding self loops (from_graph(..., self_loops=True) adds them)."""
+
+    def __init__(self, prior_degree, prior=None):
         self.prior_degree = prior_degree
         n = prior_degree.shape[0]
         self.shape = (n, n)
         self.device = prior_degree.device
+        self.prior = None
+        self._prior_csr = None
+        if prior is not None:
+            if tuple(prior.shape) != (n, n):
+                raise ValueError(f"AllPairs: prior must be [N, N] = {(n, n)} for prior_degree of shape {tuple(prior_degree.shape)}, "
+                                 f"got {tuple(prior.shape)}")
+            if prior.device != prior_degree.device:
+                raise ValueError(f"AllPairs: prior is on {prior.device} but prior_degree (shape {tuple(prior_degree.shape)}; prior shape "
+                                 f"{tuple(prior.shape)}) is on {prior_degree.device}")
+            self.prior = (prior if prior.is_sparse else prior.to_sparse()).detach().coalesce()
+            self.prior_csr()
+
+    @classmethod
+    def from_graph(cls, in_adj, self_loops=False):
+        """All-pairs candidates that see the graph `in_adj` (sparse COO or dense [N, N]): prior = in_adj, plus the identity when
+        self_loops (the reference's in_adj + I, model.py:1249-1251); prior_degree = the prior's row sums as csr_candidates computes
+        them."""
+        a = (in_adj if in_adj.is_sparse else in_adj.to_sparse()).detach()
+        if self_loops:
+            n = a.shape[0]
+            eye = torch.arange(n, device=a.device)
+            a = a + torch.sparse_coo_tensor(torch.stack([eye, eye]), torch.ones(n, device=a.device, dtype=a.dtype), a.shape)
+        a = a.coalesce()
+        return cls(csr_candidates(a)[2], prior=a)
+
+    def prior_csr(self):
+        """the prior as (rowptr int64 [N+1], col int32 [E] strictly ascending within a row, values float32 [E], erow int32 [E]);
+        built on first use and cached on the object: a later forward launches nothing for it"""
+        if self.prior is None:
+            return None
+        if self._prior_csr is None:
+            ind = self.prior.indices()
+            rowptr = torch._convert_indices_from_coo_to_csr(ind[0], self.shape[0], out_int32=False)
+            col, val = ind[1].to(torch.int32).contiguous(), self.prior.values().to(torch.float32).contiguous()
+            if col.shape[0] == 0:                # (an empty tensor has no data pointer: one entry that no row points into)
+                col, val = col.new_zeros(1), val.new_zeros(1)
+            self._prior_csr = (rowptr, col, val, ind[0].to(torch.int32).contiguous())
+        return self._prior_csr
 
 
 class EllAdjacency:

@@ -16,8 +16,13 @@
 // A later pass scores every pair of its open rows again: exact, because the score chain is the same, at the cost of one sweep per pass for
 // the rows still open (a workgroup whose rows are all settled returns before its first barrier; a wavefront whose rows are settled stages
 // tiles and keeps the barriers, but scores nothing).  The host launches ceil(maxm / MR) passes from the integer maxm: no device read-back.
+//
+// dgg_allpairs_mlp_topk_wide_prior: the same for u-v-A_uv (dgm.py:1628-1644) against a sparse PRIOR graph, as dgg_allpairs_mlp_topk_prior
+// does it on the list (dgg_prior_lookup.h: one cursor per row and wavefront, a 64-float strip of LDS per wavefront).  Every pass opens
+// the cursors of its open rows at the start of their CSR segments, so a continuation pass walks the prior again with the columns.
 #include "dgg_common.h"
 #include "dgg_edgemlp_score.h"
+#include "dgg_prior_lookup.h"
 #include "dgg_api_internal.h"
 
 using namespace dgg;
@@ -55,8 +60,10 @@ struct Args {
 
 // the lists of one row of this pass -> its chunks [c0 + m0, c0 + m0 + depth): idx / val / ex_out, the ramp, and in the row's last pass
 // rs = the lane-wise sums over ALL of its chunks in chunk order (the earlier passes' weights are read back), then the butterfly
+// PRIOR: ex_out = the prior's stored value of (i, column) (binary search in the row's segment of prp / pci / pv)
+template <bool PRIOR>
 __device__ __forceinline__ void write_row(const Args &a, const uint64_t (&list)[MR], int64_t i, int c0, int Mi, int m0, int depth, int L, float ki,
-                                          bool has_ex, int lane) {
+                                          bool has_ex, int lane, const PriorCsr &P) {
     float rsum = 0.0f;
     if (a.w) {
         for (int mg = 0; mg < m0 && (int64_t)c0 + mg < a.ccap; mg++) {
@@ -76,7 +83,11 @@ __device__ __forceinline__ void write_row(const Args &a, const uint64_t (&list)[
         const float sv = empty ? 0.0f : key_val(key);
         a.idx[e] = empty ? -1 : c;
         a.val[e] = sv;
-        if (a.ex_out) a.ex_out[e] = (has_ex && !empty) ? edge_mlp_dist_extra(a.xp + i * a.h, a.xp + (int64_t)c * a.h, a.h, a.t_ex) : 0.0f;
+        if constexpr (PRIOR) {
+            if (a.ex_out) a.ex_out[e] = empty ? 0.0f : prior_value_at(P, i, c);
+        } else {
+            if (a.ex_out) a.ex_out[e] = (has_ex && !empty) ? edge_mlp_dist_extra(a.xp + i * a.h, a.xp + (int64_t)c * a.h, a.h, a.t_ex) : 0.0f;
+        }
         if (a.w) {
             const float wv = empty ? 0.0f : ramp_weight(rk, ki, sv, a.mode);
             a.w[e] = wv;
@@ -91,9 +102,15 @@ __device__ __forceinline__ void write_row(const Args &a, const uint64_t (&list)[
 
 // VAR as in dgg_allpairs_mlp.hip -- 0: u-v-deg, 1: u-v-deg-dist, 2: edge_conv, 3: whatever the arguments say.  LDS (dynamic) as there:
 // rowsA [RB][HW] | rowsX [RB][h] (extra only) | tile (xp_v rows of h + 1 floats, then B_v transposed [HW][TN]).
-template <int HW, int VAR>
-__global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(const Args a) {
+// VAR 4 / 5 (dgg_allpairs_mlp_topk_wide_prior): the extra is the prior's stored value of the pair -- 4: LeakyReLU, no degree term
+// (u-v-A_uv); 5: whatever degree term / activation the arguments say.  LDS: rowsA | tile (B_v transposed) | strips [WAVES][64].  Every
+// pass opens its rows' cursors at the start of their segments: a continuation pass sweeps the columns, and the prior, again.  The CSR
+// arrays are the trailing arguments PR = (rowptr, col, val); the pack is empty for VAR 0..3, whose kernels are what they were.
+template <int HW, int VAR, class... PR>
+__global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(const Args a, PR... pr) {
     constexpr int RB = RW * WAVES;
+    constexpr bool PRIOR = VAR >= 4;
+    static_assert(sizeof...(PR) == (PRIOR ? 3 : 0), "the prior variants, and only they, take the prior's CSR arrays");
     extern __shared__ float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = dgg::wave_id();
     const int64_t rows = a.row1 - a.row0;
@@ -107,9 +124,10 @@ __global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(cons
         }
         return;
     }
-    const bool has_deg = VAR == 3 ? a.deg != nullptr : VAR != 2;
-    const bool has_ex = VAR == 3 ? a.ex_mode == 2 : VAR == 1;
-    const int act = VAR == 3 ? a.act : (VAR == 2 ? 0 : 1);
+    const bool has_deg = (VAR == 3 || VAR == 5) ? a.deg != nullptr : (VAR != 2 && VAR != 4);
+    const bool has_ex = VAR == 3 ? a.ex_mode == 2 : VAR == 1;     // the distance extra
+    const bool any_ex = has_ex || PRIOR;
+    const int act = (VAR == 3 || VAR == 5) ? a.act : (VAR == 2 ? 0 : 1);
     const int h = a.h, hx = h + 1;
     const int64_t N = a.N;
     float *rowsA = lds;
@@ -156,6 +174,15 @@ __global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(cons
         if (lrow < rows && a.cptr[lrow + 1] - a.cptr[lrow] > m0) open = true;
     }
     if (!open) return;
+    const PriorCsr P = prior_csr(pr...);
+    float *strip = tile + HW * TN + wave * 64;                  // (PRIOR only) this wavefront's 64 floats of prior_tile_extra
+    PriorCursor pc[PRIOR ? RW : 1];
+    if constexpr (PRIOR) {
+#pragma unroll
+        for (int r = 0; r < RW; r++) pc[r] = prior_cursor_open(P, rbase + wave * RW + r, depth[r] > 0);
+        strip[lane] = 0.0f;
+        DGG_PRIOR_WAVE_FENCE();
+    }
 
     for (int e = tid; e < RB * HW; e += WAVES * 64) {
         const int r = e / HW, c = e % HW;
@@ -201,6 +228,10 @@ __global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(cons
             tile[(c4 + 2) * TN + jj] = v.z; tile[(c4 + 3) * TN + jj] = v.w;
         }
         const float dv = (has_deg && jvalid) ? a.deg[j] : 0.0f;
+        if constexpr (PRIOR) {
+#pragma unroll
+            for (int r = 0; r < RW; r++) ex[r] = prior_tile_extra(pc[r], P, j0, strip, lane);
+        }
         __syncthreads();
         if (!wave_open) continue;                               // (wave-uniform; the barriers above are the loop's only ones)
 
@@ -215,7 +246,7 @@ __global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(cons
                 b[q] = tile[(o0 + q) * TN + lane];
                 p_du[q] = has_deg ? a.wdu[o0 + q] : 0.0f;        // (wave-uniform)
                 p_dv[q] = has_deg ? a.wdv[o0 + q] : 0.0f;
-                p_ex[q] = has_ex ? a.wex[o0 + q] : 0.0f;
+                p_ex[q] = any_ex ? a.wex[o0 + q] : 0.0f;
                 p_b1[q] = a.b1[o0 + q];
                 p_w2[q] = a.w2[o0 + q];
             }
@@ -224,7 +255,7 @@ __global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(cons
                 const float *ar = rowsA + (wave * RW + r) * HW + o0;  // wave-uniform address: LDS broadcast
 #pragma unroll
                 for (int q = 0; q < OB; q++)
-                    s[r] = edge_mlp_unit(ar[q], b[q], q, has_deg, du[r], dv, p_du, p_dv, has_ex, ex[r], p_ex, p_b1, p_w2, act, s[r]);
+                    s[r] = edge_mlp_unit(ar[q], b[q], q, has_deg, du[r], dv, p_du, p_dv, any_ex, ex[r], p_ex, p_b1, p_w2, act, s[r]);
             }
         }
 #pragma unroll
@@ -265,7 +296,7 @@ __global__ __launch_bounds__(WAVES * 64) void allpairs_mlp_topk_wide_kernel(cons
 
 #pragma unroll
     for (int r = 0; r < RW; r++)
-        if (depth[r] > 0) write_row(a, list[r], rbase + wave * RW + r, c0[r], Mi[r], m0, depth[r], L[r], ki[r], has_ex, lane);
+        if (depth[r] > 0) write_row<PRIOR>(a, list[r], rbase + wave * RW + r, c0[r], Mi[r], m0, depth[r], L[r], ki[r], has_ex, lane, P);
 }
 
 size_t lds_bytes(int hw, int h, bool has_ex) {
@@ -275,17 +306,28 @@ size_t lds_bytes(int hw, int h, bool has_ex) {
     return (rb * hw + (has_ex ? rb * h : 0) + tile) * sizeof(float);
 }
 
+size_t lds_bytes_prior(int hw) { return ((size_t)RW * WAVES * hw + (size_t)hw * TN + (size_t)WAVES * 64) * sizeof(float); }
+
+struct Prior {                    // the prior's CSR arrays (dgg_allpairs_mlp_topk_wide_prior; NULL otherwise)
+    const int64_t *prp;
+    const int32_t *pci;
+    const float *pv;
+};
+
 template <int HW, int VAR>
-void launch_passes(Args a, int maxm, hipStream_t st) {
+void launch_passes(Args a, int maxm, hipStream_t st, const Prior &pr = Prior{nullptr, nullptr, nullptr}) {
     constexpr int RB = RW * WAVES;
     const int64_t rows = a.row1 - a.row0;
     a.nrow_blocks = (unsigned)((rows + RB - 1) / RB);
     const int64_t tail = a.ccap > rows ? a.ccap - rows : 0;     // (every row has at least one chunk, or the capacity is used up)
-    const size_t lds = lds_bytes(HW, a.h, a.ex_mode == 2);
+    const size_t lds = VAR >= 4 ? lds_bytes_prior(HW) : lds_bytes(HW, a.h, a.ex_mode == 2);
     for (int p = 0; p * MR < maxm; p++) {
         a.pass = p;
         const unsigned grid = a.nrow_blocks + (p == 0 ? (unsigned)((tail + WAVES - 1) / WAVES) : 0u);
-        hipLaunchKernelGGL((allpairs_mlp_topk_wide_kernel<HW, VAR>), dim3(grid), dim3(WAVES * 64), lds, st, a);
+        if constexpr (VAR >= 4)
+            hipLaunchKernelGGL((allpairs_mlp_topk_wide_kernel<HW, VAR, const int64_t *, const int32_t *, const float *>), dim3(grid), dim3(WAVES * 64), lds, st, a, pr.prp, pr.pci, pr.pv);
+        else
+            hipLaunchKernelGGL((allpairs_mlp_topk_wide_kernel<HW, VAR>), dim3(grid), dim3(WAVES * 64), lds, st, a);
     }
 }
 
@@ -296,6 +338,12 @@ void launch_var(const Args &a, int maxm, hipStream_t st) {
     else if (a.deg && leaky && a.ex_mode == 2) launch_passes<HW, 1>(a, maxm, st);
     else if (!a.deg && !leaky && a.ex_mode == 0) launch_passes<HW, 2>(a, maxm, st);
     else launch_passes<HW, 3>(a, maxm, st);
+}
+
+template <int HW>
+void launch_var_prior(const Args &a, int maxm, hipStream_t st, const Prior &pr) {
+    if (!a.deg && a.act == 1) launch_passes<HW, 4>(a, maxm, st, pr);
+    else launch_passes<HW, 5>(a, maxm, st, pr);
 }
 
 bool width_ok(int w) { return w == 16 || w == 32 || w == 64 || w == 128; }
@@ -339,4 +387,46 @@ extern "C" int dgg_allpairs_mlp_topk_wide(const float *AB, const float *xp, int6
         default: launch_var<128>(a, maxm, st); break;
     }
     return dgg_check_launch("allpairs_mlp_topk_wide");
+}
+
+extern "C" int dgg_allpairs_mlp_topk_wide_prior(const float *AB, const float *xp, int64_t N, int h, int hw, int64_t row0, int64_t row1,
+                                                const float *deg, int ex_mode, float t_ex, const float *wdu, const float *wdv,
+                                                const float *wex, const float *b1, const float *w2, const float *b2, int act, int noise_mode,
+                                                const float *G, int64_t ldG, uint32_t s0, uint32_t s1, const float *k, int mode, int maxm,
+                                                const int32_t *cptr, int64_t ccap, int32_t *idx, float *val, float *ex_out, float *w, float *rs,
+                                                const int64_t *prior_rowptr, const int32_t *prior_col, const float *prior_val, void *stream) {
+    if (!width_ok(hw) || !width_ok(h))
+        return dgg_set_error(DGG_ERR_UNSUPPORTED, "allpairs_mlp_topk_wide_prior: hidden width hw and latent_dim h must be 16, 32, 64 or 128");
+    if (ex_mode != 1)
+        return dgg_set_error(DGG_ERR_UNSUPPORTED, "allpairs_mlp_topk_wide_prior: ex_mode must be 1 (the extra of a pair is the prior's stored "
+                                                  "value); ex_mode 0 / 2 are dgg_allpairs_mlp_topk_wide's");
+    if (noise_mode == 4 || noise_mode == 5)
+        return dgg_set_error(DGG_ERR_UNSUPPORTED, "allpairs_mlp_topk_wide_prior: noise_mode must be none / explicit / hash / symmetric hash "
+                                                  "(every pair is scored: the ranked generators have nothing to stop early)");
+    if (noise_mode < 0 || noise_mode > 5) return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: unknown noise_mode");
+    if (act != 0 && act != 1) return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: act must be 0 (identity) or 1 (LeakyReLU)");
+    if (mode != 0 && mode != 1 && mode != 3)
+        return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: mode must be 0 (k_times_edge_prob), 1 (k_only) or 3 (straight-through forward)");
+    if (noise_mode == 1 && (!G || ldG < N)) return dgg_set_error(DGG_ERR_ARG, "explicit noise requested but G is NULL (or ldG < N)");
+    if (row0 < 0 || row1 < row0 || row1 > N || N >= ((int64_t)1 << 31))
+        return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: rows must satisfy 0 <= row0 <= row1 <= N < 2^31");
+    if (maxm < 1 || maxm > DGG_CHUNK_MAXM_ANY || ccap < 0 || ccap >= ((int64_t)1 << 25))
+        return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: maxm in 1..2^20, 0 <= ccap < 2^25 chunks");
+    if (!prior_rowptr || !prior_col || !prior_val)
+        return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: the prior's CSR arrays (rowptr, col, val) must not be NULL");
+    if (row0 == row1) return 0;
+    if (!AB || !wex || !b1 || !w2 || !b2 || !k || !cptr || !idx || !val || (w && !rs) || (deg && (!wdu || !wdv)))
+        return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: missing inputs / weights / layout for the requested mode");
+    if ((reinterpret_cast<uintptr_t>(AB) & 15) != 0) return dgg_set_error(DGG_ERR_ARG, "allpairs_mlp_topk_wide_prior: AB must be 16-byte aligned");
+    const Args a{AB, xp, N, h, row0, row1, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, noise_mode, G, ldG, s0, s1, k, mode, cptr, ccap,
+                 idx, val, ex_out, w, rs, 0, 0u};
+    const Prior pr{prior_rowptr, prior_col, prior_val};
+    const hipStream_t st = (hipStream_t)stream;
+    switch (hw) {
+        case 16: launch_var_prior<16>(a, maxm, st, pr); break;
+        case 32: launch_var_prior<32>(a, maxm, st, pr); break;
+        case 64: launch_var_prior<64>(a, maxm, st, pr); break;
+        default: launch_var_prior<128>(a, maxm, st, pr); break;
+    }
+    return dgg_check_launch("allpairs_mlp_topk_wide_prior");
 }

@@ -268,7 +268,10 @@ class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
     prior degrees only): the scorer, the perturbation and the top-K run as one kernel over the complete candidate pattern
     (dgg_allpairs_mlp_topk; no [N,N] array), with the bits of edge_mlp_fwd + edgelist_topk_p on that pattern.  From the 64-rank list
     on everything is the edge-list node's code: the ramp, and the backward on the ELL block with eid = the slot index into the
-    per-entry extras the kernel returned."""
+    per-entry extras the kernel returned.
+    cfg["prior"] = (rowptr, col, val), with cfg["ex_mode"] = 1: u-v-A_uv against a sparse prior graph (dgg_allpairs_mlp_topk_prior) -- the
+    extra of a kept entry is the prior's stored value, returned per entry like the distance term's; the prior's values are data and get
+    no gradient (dwex comes from edge_mlp_score_bwd as on edge lists)."""
 
     @staticmethod
     def forward(ctx, x, k, deg, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
@@ -276,7 +279,7 @@ class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
         AB = ops.linear_fwd(xp, Wcat, None, ops.ACT_NONE)
         sdeg = deg if wdu is not None else None
         idx, val, ex = ops.allpairs_mlp_topk(AB, xp, sdeg, cfg["ex_mode"], cfg["t_ex"], wdu, wdv, wex, eb1, w2, b2, cfg["act"], cfg["K"],
-                                             cfg["noise_mode"], cfg["G"], cfg["seed"])
+                                             cfg["noise_mode"], cfg["G"], cfg["seed"], prior=cfg.get("prior"))
         w, rs = ops.softk_fwd(idx, val, k, cfg.get("fwd_mode", cfg["mode"]))
         ctx.cfg = cfg
         ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in (sdeg, ex, wdu, wdv, wex))
@@ -303,7 +306,8 @@ class _DGGAllPairsMlpWideAdjFn(torch.autograd.Function):
     an unbounded degree, dgm.py:1402-1421, 1580-1584).  Forward: dgg_allpairs_mlp_topk_wide on cfg["layout"] (ops.chunk_layout) -- row i
     keeps ceil(k_i + 8.5) + 1 ranks in chunks of 64, the ramp fused.  Backward: the ramp on chunked rows (softk_bwd_chunked), then the
     edge-list node's scorer backward in its CSR form on the flattened chunks (row i's entries are [64 cptr[i], 64 cptr[i+1]); empty
-    slots carry idx = -1 and are skipped), the distance term of u-v-deg-dist through csr_uvdist_bwd on the same pattern."""
+    slots carry idx = -1 and are skipped), the distance term of u-v-deg-dist through csr_uvdist_bwd on the same pattern.
+    cfg["prior"] with cfg["ex_mode"] = 1: as _DGGAllPairsMlpAdjFn (dgg_allpairs_mlp_topk_wide_prior)."""
 
     @staticmethod
     def forward(ctx, x, k, deg, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
@@ -312,7 +316,8 @@ class _DGGAllPairsMlpWideAdjFn(torch.autograd.Function):
         sdeg = deg if wdu is not None else None
         lay = cfg["layout"]
         idx, val, ex, w, rs = ops.allpairs_mlp_topk_wide(AB, xp, sdeg, cfg["ex_mode"], cfg["t_ex"], wdu, wdv, wex, eb1, w2, b2, cfg["act"], k, lay,
-                                                         cfg.get("fwd_mode", cfg["mode"]), cfg["noise_mode"], cfg["G"], cfg["seed"])
+                                                         cfg.get("fwd_mode", cfg["mode"]), cfg["noise_mode"], cfg["G"], cfg["seed"],
+                                                         prior=cfg.get("prior"))
         ctx.cfg = cfg
         ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in (sdeg, ex, wdu, wdv, wex))
         ctx.save_for_backward(x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2)
@@ -384,6 +389,7 @@ class _DGGScoresFn(torch.autograd.Function):
 _PAD_CACHE = {}
 _EDGE_MLP_FUSED = ("u-v-deg", "u-v-A_uv", "u-v-deg-dist", "edge_conv", "A_uv")     # edge-MLP scorers the fused layer covers
 _EDGE_MLP_ALLPAIRS = ("u-v-deg", "u-v-deg-dist", "edge_conv")     # ... that read the end nodes and their degrees only: all-pairs candidates
+_EDGE_MLP_ALLPAIRS_PRIOR = ("u-v-A_uv",)     # ... that read the input graph's values: all-pairs candidates that carry a prior (AllPairs(deg, prior=))
 
 
 def _pad_features(x, params, keys):
@@ -775,7 +781,8 @@ class DGG_LearnableK_debug(nn.Module):
             # their autograd edges (a differentiable unnorm_adj) and this clause in fused_fallback
             ("edge-MLP scorer on all-pairs candidates",
              mlp_mode and isinstance(in_adj, AllPairs) and not getattr(a, "dgg_allpairs_mlp_fused", False)),
-            # (all-pairs candidates have no stored values: u-v-A_uv / A_uv raise in forward(), where the separate modules send them)
+            # (all-pairs candidates without a prior have no stored values: u-v-A_uv / A_uv raise in forward(), where the separate modules
+            #  send them; with a prior -- AllPairs(deg, prior=) -- u-v-A_uv runs there, and stays outside the fused layer: a follow-up)
             ("edge-MLP scorer on all-pairs candidates that reads the stored values of in_adj (u-v-A_uv / A_uv)",
              mlp_mode and isinstance(in_adj, AllPairs) and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS),
             # (dgg_allpairs_mlp_topk is built for these widths; edge_conv's hidden width is latent_dim / 2)
@@ -978,7 +985,7 @@ class DGG_LearnableK_debug(nn.Module):
             return {"ell": "list", "csr": "csr"}.get(policy, "csr_when_needed")
         if self._chunk_policy(noise_mode):
             return "chunked"
-        if self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS:     # (the edge-MLP scorers on all-pairs candidates: an opt-in of their own)
+        if self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS + _EDGE_MLP_ALLPAIRS_PRIOR:     # (the edge-MLP scorers on all-pairs candidates -- u-v-A_uv: with a prior -- have an opt-in of their own)
             return "chunked" if self._allpairs_mlp_chunked() else "list"
         if policy in ("ell", "chunked") or N > int(getattr(self.args, "dgg_allpairs_csr_max", 8192)):
             return "list"
@@ -1255,10 +1262,17 @@ class DGG_LearnableK_debug(nn.Module):
             p = ops.CsrPerturbFn.apply(p, pattern[0], pattern[1], pattern[2], x.shape[0], noise_mode, G, seed)
         return CsrAdjacency(pattern[0], pattern[1], pattern[2], p, x.shape[0])
 
+    def _scorer_prior(self, prior):
+        """the prior's CSR arrays for a scorer that reads them (u-v-A_uv), else None: the other scorers ignore a prior"""
+        return prior[:3] if (prior is not None and self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS_PRIOR) else None
+
     def forward(self, x, in_adj, noise=True, writer=None, epoch=None):
         """x [N,dim] fp32 on the GPU; in_adj: sparse COO [N,N] (coalesced, self loops added by the caller) whose
         stored entries are the candidate edges, or `AllPairs(prior_degree)`.  `noise` is accepted and ignored
-        exactly like the reference (perturbation is gated by args.perturb_edge_prob only, dgm.py:1211)."""
+        exactly like the reference (perturbation is gated by args.perturb_edge_prob only, dgm.py:1211).
+        `AllPairs(prior_degree, prior=P)`: every pair is a candidate and the input graph P is seen -- the scorer u-v-A_uv reads P's
+        stored value of a pair (0 for a non-edge) and the k-net gcn-x-deg aggregates over P; the reference equivalent is the complete
+        in_adj that stores P's values.  P is used as given (no self loops are added)."""
         assert x.ndim == 2 and len(in_adj.shape) == 2
         if self.edge_prob_net_mode != "u-v-dist" and self.edge_prob_net_mode not in _EDGE_MLP_MODES:
             raise Exception("mode not found")
@@ -1271,8 +1285,14 @@ class DGG_LearnableK_debug(nn.Module):
         if self.args.debug_step in (0, 1) or self.k_select_mode == "edge_p-cdf":
             return self._scores_adjacency(x, in_adj)
         avals = erow = None
+        prior = in_adj.prior_csr() if isinstance(in_adj, AllPairs) else None
         if isinstance(in_adj, AllPairs):
-            if self.edge_prob_net_mode != "u-v-dist" and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS:
+            if self.edge_prob_net_mode == "A_uv" and prior is not None:
+                raise NotImplementedError("all-pairs candidates with a prior: the scorer 'A_uv' (hidden width 1, outside the kernel's widths) is "
+                                          "a function of the prior entry only, so every non-edge of a row ties and the selection degenerates "
+                                          "to 'prior edges, then lowest columns'; use 'u-v-A_uv' (or edge-list candidates)")
+            if self.edge_prob_net_mode != "u-v-dist" and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS and not (
+                    prior is not None and self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS_PRIOR):
                 raise NotImplementedError(f"all-pairs candidates are defined for 'u-v-dist' and the edge-MLP scorers {_EDGE_MLP_ALLPAIRS} "
                                           f"only: {self.edge_prob_net_mode!r} reads the stored values of in_adj (dgm.py:1628-1644, "
                                           "1720-1725), which all-pairs candidates do not have")
@@ -1281,6 +1301,10 @@ class DGG_LearnableK_debug(nn.Module):
                 # (the widths dgg_allpairs_mlp_topk is built for; edge_conv's hidden width is latent_dim / 2)
                 raise NotImplementedError(f"edge-MLP scorers {_EDGE_MLP_ALLPAIRS} on all-pairs candidates: latent_dim in (16, 32, 64, 128) "
                                           "(edge_conv: from 32), ell_width <= 64")
+            if self.k_net_mode == "gcn-x-deg" and prior is None:
+                raise NotImplementedError("k-net mode 'gcn-x-deg' aggregates over the stored entries of in_adj, which all-pairs candidates "
+                                          "do not have (k-net modes 'x', 'input_deg', 'learn_normalized_degree' run on them; "
+                                          "AllPairs(prior_degree, prior=graph) carries the entries)")
             cand, deg = None, in_adj.prior_degree
         else:
             if isinstance(in_adj, EllAdjacency):     # dgg_adj_input != "input_adj": previous learned graph
@@ -1319,11 +1343,11 @@ class DGG_LearnableK_debug(nn.Module):
         if self.k_net_mode in ("x", "gcn-x-deg"):
             xp_dual, xk = self._project_for_k(x, literal)
             if self.k_net_mode == "gcn-x-deg":       # relu(normalize_adj(in_adj) @ xk @ k_W)   (dgm.py:1528-1540)
-                if cand is None:
-                    raise NotImplementedError("k-net mode 'gcn-x-deg' aggregates over the stored entries of in_adj, which all-pairs candidates "
-                                              "do not have (k-net modes 'x', 'input_deg', 'learn_normalized_degree' run on them)")
-                pat = csr_pattern(in_adj)
-                nadj = CsrAdjacency(pat[0], pat[1], pat[2], in_adj.coalesce().values().float(), x.shape[0]).normalize()
+                if cand is None:                 # all-pairs candidates that carry a prior: normalize_adj(prior) @ xk on the prior's pattern
+                    nadj = CsrAdjacency(prior[0], prior[1], prior[3], prior[2], x.shape[0]).normalize()
+                else:
+                    pat = csr_pattern(in_adj)
+                    nadj = CsrAdjacency(pat[0], pat[1], pat[2], in_adj.coalesce().values().float(), x.shape[0]).normalize()
                 xk = ops.LinearFn.apply(nadj.matmul(xk), self.k_W, None, ops.ACT_RELU, 1)
             if getattr(self.args, "stochastic_k", False) and self.training:
                 k = self._stochastic_k(torch.cat([xk, self._norm_deg(deg, None, 1e-5)[0].unsqueeze(1)], 1), deg, None, embed=True)
@@ -1359,7 +1383,7 @@ class DGG_LearnableK_debug(nn.Module):
             lay = ops.chunk_layout(k.detach(), ncols=x.shape[0])          # (one readback: the chunk count sizes the arrays)
             if lay is not None and lay.wide:
                 mlp, _ = self._edge_mlp_terms(None)
-                cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], layout=lay)
+                cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], layout=lay, prior=self._scorer_prior(prior))
                 w, idx, val, rs = _DGGAllPairsMlpWideAdjFn.apply(x, k, deg, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"],
                                                                  mlp["w2"], mlp["b2"], cfg)
                 self._log_first_k_chunked(writer, epoch, cfg, w, val, lay)
@@ -1379,8 +1403,8 @@ class DGG_LearnableK_debug(nn.Module):
             cfg["want_bwd"] = ops.backward_will_follow(x, k, We, be)
             w, idx, val, rs = _DGGSoftAdjFn.apply(x, k, We, be, cfg)
         elif cand is None:                       # u-v-deg / u-v-deg-dist / edge_conv on all-pairs candidates: the prior degrees are the degrees
-            mlp, _ = self._edge_mlp_terms(None)
-            cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
+            mlp, _ = self._edge_mlp_terms(None)  # (u-v-A_uv: the extra of a pair is the prior's stored value, looked up inside the sweep)
+            cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], prior=self._scorer_prior(prior))
             w, idx, val, rs = _DGGAllPairsMlpAdjFn.apply(x, k, deg, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"],
                                                          mlp["w2"], mlp["b2"], cfg)
         else:

@@ -683,13 +683,27 @@ def edgelist_topk_p(p_edge, N, rowptr, col, K=DEFAULT_K, noise_mode=NOISE_NONE, 
     return idx, val, eid
 
 
+def _prior_arrays(prior, N):
+    """the CSR arrays of a prior graph as the *_prior entry points take them; an empty prior (nnz = 0) gets one-element col / val arrays
+    that no row points into (an empty tensor has no data pointer)"""
+    prp, pci, pv = prior
+    prp, pci, pv = _chk(prp, torch.int64), _chk(pci, torch.int32), _chk(pv)
+    assert prp.shape[0] == N + 1 and pci.shape == pv.shape, "prior: rowptr [N+1] and col / val of one length"
+    if pci.shape[0] == 0:
+        pci, pv = torch.zeros((1,), device=prp.device, dtype=torch.int32), torch.zeros((1,), device=prp.device, dtype=torch.float32)
+    return prp, pci, pv
+
+
 def allpairs_mlp_topk(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act=ACT_LEAKY, K=DEFAULT_K, noise_mode=NOISE_NONE, G=None,
-                      seed=(0, 0), rows=None, out=None):
+                      seed=(0, 0), rows=None, out=None, prior=None):
     """edge-MLP scorer (u-v-deg / u-v-deg-dist / edge_conv) + perturbation + per-row top-K on ALL-PAIRS candidates in one kernel
     (dgg_allpairs_mlp_topk): the bits of edge_mlp_fwd + edgelist_topk_p on the complete pattern, without its N^2 arrays
     -> idx, val [r1-r0, K], ex [r1-r0, K] (the extra of each selected entry; None for ex_mode 0).
     deg [N] (None: edge_conv) = the prior degrees; rows = (r0, r1): those rows only (AB, xp, deg stay every node's, G stays [N, N]).
-    out = (idx, val, ex): write into these tensors (tests: canaried buffers) instead of fresh ones."""
+    out = (idx, val, ex): write into these tensors (tests: canaried buffers) instead of fresh ones.
+    prior = (rowptr int64 [N+1], col int32, val float32): the CSR arrays of a sparse prior graph, columns strictly ascending within a row
+    (AllPairs.prior_csr()) -- with ex_mode 1 the extra of a pair is the prior's stored value, 0 where nothing is stored (u-v-A_uv on the
+    complete pattern, dgg_allpairs_mlp_topk_prior); ex = the prior value of every kept entry.  The arrays stay the whole graph's under rows=."""
     AB, xp = _chk(AB), _chk(xp)
     N, h = xp.shape
     hw = AB.shape[1] // 2
@@ -706,6 +720,13 @@ def allpairs_mlp_topk(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act
         G = _chk(G)
         ldG = G.shape[-1]
     o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
+    if prior is not None:
+        prp, pci, pv = _prior_arrays(prior, N)
+        _lib.check(_lib.lib().dgg_allpairs_mlp_topk_prior(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
+                                                          _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act,
+                                                          noise_mode, _ptr(G), ldG, seed[0], seed[1], K, _ptr(idx), _ptr(val), _ptr(ex),
+                                                          _ptr(prp), _ptr(pci), _ptr(pv), _stream()), "allpairs_mlp_topk_prior")
+        return idx, val, ex
     _lib.check(_lib.lib().dgg_allpairs_mlp_topk(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
                                                 _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act, noise_mode,
                                                 _ptr(G), ldG, seed[0], seed[1], K, _ptr(idx), _ptr(val), _ptr(ex), _stream()),
@@ -718,13 +739,13 @@ APMLP_WIDE_REG_CHUNKS = 8     # chunks of a row that one sweep of dgg_allpairs_m
 
 
 def allpairs_mlp_topk_wide(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, k, layout, mode=MODE_K_TIMES_EDGE_PROB,
-                           noise_mode=NOISE_NONE, G=None, seed=(0, 0), rows=None, out=None):
+                           noise_mode=NOISE_NONE, G=None, seed=(0, 0), rows=None, out=None, prior=None):
     """allpairs_mlp_topk for rows of ANY width, on chunked rows with the ramp fused (dgg_allpairs_mlp_topk_wide): row i keeps its
     ceil(k_i + 8.5) + 1 best columns in the chunks of `layout` = chunk_layout(k of these rows, ncols=N)
     -> idx, val, ex [chunks,64] (ex None for ex_mode 0), w [chunks,64], rs [r1-r0].  mode: MODE_K_TIMES_EDGE_PROB / MODE_K_ONLY /
     MODE_HARD_ST.  rows = (r0, r1): those rows only (k and layout are theirs; AB, xp, deg stay every node's, G stays [N, N]).
     out = (idx, val, ex, w, rs): write into these tensors (tests: canaried buffers of any capacity >= layout.chunks; the spare chunks
-    come back empty) instead of fresh ones."""
+    come back empty) instead of fresh ones.  prior = (rowptr, col, val): as allpairs_mlp_topk (dgg_allpairs_mlp_topk_wide_prior)."""
     AB, xp, k = _chk(AB), _chk(xp), _chk(k)
     N, h = xp.shape
     hw = AB.shape[1] // 2
@@ -747,6 +768,14 @@ def allpairs_mlp_topk_wide(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2
         G = _chk(G)
         ldG = G.shape[-1]
     o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
+    if prior is not None:
+        prp, pci, pv = _prior_arrays(prior, N)
+        _lib.check(_lib.lib().dgg_allpairs_mlp_topk_wide_prior(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex),
+                                                               _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)),
+                                                               _ptr(_chk(b2)), act, noise_mode, _ptr(G), ldG, seed[0], seed[1], _ptr(k), mode,
+                                                               layout.maxm, _ptr(layout.cptr), C_, _ptr(idx), _ptr(val), _ptr(ex), _ptr(w),
+                                                               _ptr(rs), _ptr(prp), _ptr(pci), _ptr(pv), _stream()), "allpairs_mlp_topk_wide_prior")
+        return idx, val, ex, w, rs
     _lib.check(_lib.lib().dgg_allpairs_mlp_topk_wide(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
                                                      _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act, noise_mode,
                                                      _ptr(G), ldG, seed[0], seed[1], _ptr(k), mode, layout.maxm, _ptr(layout.cptr), C_,
