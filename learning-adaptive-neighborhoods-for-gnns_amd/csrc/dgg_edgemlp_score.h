@@ -1,5 +1,6 @@
 // dgg_edgemlp_score.h -- the score chain of the edge-MLP scorers (reference dgm.py:1628-1725), shared by every kernel that evaluates
-// it (dgg_edgemlp.hip on a candidate edge list, dgg_allpairs_mlp.hip on all-pairs candidates) so that they return the same bits:
+// it (dgg_edgemlp.hip on a candidate edge list; dgg_allpairs_mlp_sweep.h, the sweep of dgg_allpairs_mlp.hip and dgg_allpairs_mlp_wide.hip
+// on all-pairs candidates) so that they return the same bits:
 //   z_o = A[u][o] + B[v][o] (+ deg_u wdu_o + deg_v wdv_o) (+ ex wex_o) + b1_o;  p = sigmoid(sum_o act(z_o) w2_o + b2)
 // in exactly the operation order of oracle/dgg_oracle.c (mlp_edge_p); the sum over o ascends.
 #pragma once

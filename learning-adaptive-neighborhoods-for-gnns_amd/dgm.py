@@ -228,6 +228,26 @@ def _mlp_score_bwd(ctx, terms, xp, AB, idx, eid, val, dval, ex, perturb, i_wcat,
     return dxp, dex, tuple(gs[k_] for k_ in _SC_KEYS)
 
 
+def _mlp_adj_inputs(x, deg, We, be, Wcat, wdu):
+    """prologue of the three nodes below -> xp, the per-node products AB = xp [Wa | Wb]^T, the prior degrees if the scorer reads them"""
+    xp = ops.linear_fwd(x, We, be, ops.ACT_LEAKY)
+    return xp, ops.linear_fwd(xp, Wcat, None, ops.ACT_NONE), (deg if wdu is not None else None)
+
+
+def _mlp_adj_save(ctx, cfg, opt, saved, nondiff):
+    """what the three nodes below keep.  opt = (sdeg, ex, wdu, wdv, wex): None allowed, so kept outside save_for_backward, detached"""
+    ctx.cfg = cfg
+    ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in opt)
+    ctx.save_for_backward(*saved)
+    ctx.mark_non_differentiable(*nondiff)
+
+
+def _mlp_adj_grads(ctx, x, We, xp, dxp, dk, gsc, n_data):
+    """backward tail of the three nodes below -> gradients of (x, k, n_data inputs that get none, We, be, the scorer's terms, cfg)"""
+    dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
+    return (dx, dk) + (None,) * n_data + (dWe, dbe) + gsc + (None,)
+
+
 class _DGGEdgeMlpAdjFn(torch.autograd.Function):
     """Same generator with an edge-MLP scorer on edge-list candidates (reference dgm.py:1628-1725).  The first MLP layer
     is split into per-node products AB = xp [Wa | Wb]^T (MFMA GEMM) and per-edge terms (include/dgg_hip.h,
@@ -236,19 +256,13 @@ class _DGGEdgeMlpAdjFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, k, deg, ex_in, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
-        xp = ops.linear_fwd(x, We, be, ops.ACT_LEAKY)
+        xp, AB, sdeg = _mlp_adj_inputs(x, deg, We, be, Wcat, wdu)
         rowptr, col, erow = cfg["cand"]
-        AB = ops.linear_fwd(xp, Wcat, None, ops.ACT_NONE)
-        sdeg = deg if wdu is not None else None
         p_edge, ex = ops.edge_mlp_fwd(AB, xp, erow, col, sdeg, ex_in, cfg["ex_mode"], cfg["t_ex"], wdu, wdv, wex, eb1, w2, b2,
                                       cfg["act"])
         idx, val, eid = ops.edgelist_topk_p(p_edge, x.shape[0], rowptr, col, cfg["K"], cfg["noise_mode"], cfg["G"], cfg["seed"])
         w, rs = ops.softk_fwd(idx, val, k, cfg.get("fwd_mode", cfg["mode"]))
-        ctx.cfg = cfg
-        # optional tensors (None allowed): kept outside save_for_backward, detached
-        ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in (sdeg, ex, wdu, wdv, wex))
-        ctx.save_for_backward(x, We, xp, k, idx, val, eid, AB, Wcat, eb1, w2, b2)
-        ctx.mark_non_differentiable(idx, val, rs)
+        _mlp_adj_save(ctx, cfg, (sdeg, ex, wdu, wdv, wex), (x, We, xp, k, idx, val, eid, AB, Wcat, eb1, w2, b2), (idx, val, rs))
         return w, idx, val, rs
 
     @staticmethod
@@ -259,8 +273,7 @@ class _DGGEdgeMlpAdjFn(torch.autograd.Function):
         dxp, dex, gsc = _mlp_score_bwd(ctx, terms, xp, AB, idx, eid, val, dval, ctx.opt[1], cfg["noise_mode"] != ops.NOISE_NONE, 6)
         if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
             dxp = dxp + ops.edge_bwd(xp, idx, val, dex, t=cfg["t_ex"], perturb=False)
-        dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
-        return (dx, dk, None, None, dWe, dbe) + gsc + (None,)
+        return _mlp_adj_grads(ctx, x, We, xp, dxp, dk, gsc, 2)                     # (deg, ex_in)
 
 
 class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
@@ -275,16 +288,11 @@ class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, k, deg, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
-        xp = ops.linear_fwd(x, We, be, ops.ACT_LEAKY)
-        AB = ops.linear_fwd(xp, Wcat, None, ops.ACT_NONE)
-        sdeg = deg if wdu is not None else None
+        xp, AB, sdeg = _mlp_adj_inputs(x, deg, We, be, Wcat, wdu)
         idx, val, ex = ops.allpairs_mlp_topk(AB, xp, sdeg, cfg["ex_mode"], cfg["t_ex"], wdu, wdv, wex, eb1, w2, b2, cfg["act"], cfg["K"],
                                              cfg["noise_mode"], cfg["G"], cfg["seed"], prior=cfg.get("prior"))
         w, rs = ops.softk_fwd(idx, val, k, cfg.get("fwd_mode", cfg["mode"]))
-        ctx.cfg = cfg
-        ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in (sdeg, ex, wdu, wdv, wex))
-        ctx.save_for_backward(x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2)
-        ctx.mark_non_differentiable(idx, val, rs)
+        _mlp_adj_save(ctx, cfg, (sdeg, ex, wdu, wdv, wex), (x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2), (idx, val, rs))
         return w, idx, val, rs
 
     @staticmethod
@@ -297,8 +305,7 @@ class _DGGAllPairsMlpAdjFn(torch.autograd.Function):
         dxp, dex, gsc = _mlp_score_bwd(ctx, terms, xp, AB, idx, eid, val, dval, ex, cfg["noise_mode"] != ops.NOISE_NONE, 5)
         if cfg["ex_mode"] == 2:                          # exp(t ||xp_u - xp_v||) also depends on the projection
             dxp = dxp + ops.edge_bwd(xp, idx, val, dex, t=cfg["t_ex"], perturb=False)
-        dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
-        return (dx, dk, None, dWe, dbe) + gsc + (None,)
+        return _mlp_adj_grads(ctx, x, We, xp, dxp, dk, gsc, 1)                     # (deg)
 
 
 class _DGGAllPairsMlpWideAdjFn(torch.autograd.Function):
@@ -311,17 +318,12 @@ class _DGGAllPairsMlpWideAdjFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, k, deg, We, be, Wcat, wdu, wdv, wex, eb1, w2, b2, cfg):
-        xp = ops.linear_fwd(x, We, be, ops.ACT_LEAKY)
-        AB = ops.linear_fwd(xp, Wcat, None, ops.ACT_NONE)
-        sdeg = deg if wdu is not None else None
+        xp, AB, sdeg = _mlp_adj_inputs(x, deg, We, be, Wcat, wdu)
         lay = cfg["layout"]
         idx, val, ex, w, rs = ops.allpairs_mlp_topk_wide(AB, xp, sdeg, cfg["ex_mode"], cfg["t_ex"], wdu, wdv, wex, eb1, w2, b2, cfg["act"], k, lay,
                                                          cfg.get("fwd_mode", cfg["mode"]), cfg["noise_mode"], cfg["G"], cfg["seed"],
                                                          prior=cfg.get("prior"))
-        ctx.cfg = cfg
-        ctx.opt = tuple(None if t_ is None else t_.detach() for t_ in (sdeg, ex, wdu, wdv, wex))
-        ctx.save_for_backward(x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2)
-        ctx.mark_non_differentiable(idx, val, rs)
+        _mlp_adj_save(ctx, cfg, (sdeg, ex, wdu, wdv, wex), (x, We, xp, k, idx, val, AB, Wcat, eb1, w2, b2), (idx, val, rs))
         return w, idx, val, rs
 
     @staticmethod
@@ -339,8 +341,7 @@ class _DGGAllPairsMlpWideAdjFn(torch.autograd.Function):
             # (empty slots: ex = 0 from the forward and dex = 0 from edge_mlp_bwd's CSR form, so csr_uvdist_bwd skips them before it reads
             #  the column; the clamp only keeps a column it never uses inside the graph)
             dxp = dxp + ops.csr_uvdist_bwd(xp, rowptr, col.clamp(min=0), ex, dex, t=cfg["t_ex"])
-        dx, dWe, dbe = ops.linear_bwd(x, We, xp, dxp, ops.ACT_LEAKY, need_dx=ctx.needs_input_grad[0])
-        return (dx, dk, None, dWe, dbe) + gsc + (None,)
+        return _mlp_adj_grads(ctx, x, We, xp, dxp, dk, gsc, 1)                     # (deg)
 
 
 class _DGGScoresFn(torch.autograd.Function):

@@ -694,6 +694,23 @@ def _prior_arrays(prior, N):
     return prp, pci, pv
 
 
+def _apmlp_args(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, noise_mode, G, seed, rows, prior):
+    """the checks and the leading arguments (AB .. seed[1]) that the four dgg_allpairs_mlp_topk* entry points share
+    -> (r0, r1), the argument tuple, the symbol's suffix ("" / "_prior") and the prior's CSR arrays (the entry's trailing pointers)"""
+    AB, xp = _chk(AB), _chk(xp)
+    N, h = xp.shape
+    hw = AB.shape[1] // 2
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    ldG = 0
+    if G is not None:
+        G = _chk(G)
+        ldG = G.shape[-1]
+    o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
+    lead = (_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)),
+            _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act, noise_mode, _ptr(G), ldG, seed[0], seed[1])
+    return (r0, r1), lead, ("" if prior is None else "_prior"), (() if prior is None else _prior_arrays(prior, N))
+
+
 def allpairs_mlp_topk(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act=ACT_LEAKY, K=DEFAULT_K, noise_mode=NOISE_NONE, G=None,
                       seed=(0, 0), rows=None, out=None, prior=None):
     """edge-MLP scorer (u-v-deg / u-v-deg-dist / edge_conv) + perturbation + per-row top-K on ALL-PAIRS candidates in one kernel
@@ -704,10 +721,7 @@ def allpairs_mlp_topk(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act
     prior = (rowptr int64 [N+1], col int32, val float32): the CSR arrays of a sparse prior graph, columns strictly ascending within a row
     (AllPairs.prior_csr()) -- with ex_mode 1 the extra of a pair is the prior's stored value, 0 where nothing is stored (u-v-A_uv on the
     complete pattern, dgg_allpairs_mlp_topk_prior); ex = the prior value of every kept entry.  The arrays stay the whole graph's under rows=."""
-    AB, xp = _chk(AB), _chk(xp)
-    N, h = xp.shape
-    hw = AB.shape[1] // 2
-    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    (r0, r1), lead, sfx, pr = _apmlp_args(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, noise_mode, G, seed, rows, prior)
     if out is None:
         n = max(r1 - r0, 0)
         idx = torch.empty((n, K), device=xp.device, dtype=torch.int32)
@@ -715,22 +729,8 @@ def allpairs_mlp_topk(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act
         ex = torch.empty((n, K), device=xp.device, dtype=torch.float32) if ex_mode else None
     else:
         idx, val, ex = out
-    ldG = 0
-    if G is not None:
-        G = _chk(G)
-        ldG = G.shape[-1]
-    o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
-    if prior is not None:
-        prp, pci, pv = _prior_arrays(prior, N)
-        _lib.check(_lib.lib().dgg_allpairs_mlp_topk_prior(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
-                                                          _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act,
-                                                          noise_mode, _ptr(G), ldG, seed[0], seed[1], K, _ptr(idx), _ptr(val), _ptr(ex),
-                                                          _ptr(prp), _ptr(pci), _ptr(pv), _stream()), "allpairs_mlp_topk_prior")
-        return idx, val, ex
-    _lib.check(_lib.lib().dgg_allpairs_mlp_topk(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
-                                                _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act, noise_mode,
-                                                _ptr(G), ldG, seed[0], seed[1], K, _ptr(idx), _ptr(val), _ptr(ex), _stream()),
-               "allpairs_mlp_topk")
+    _lib.check(getattr(_lib.lib(), "dgg_allpairs_mlp_topk" + sfx)(*lead, K, _ptr(idx), _ptr(val), _ptr(ex), *map(_ptr, pr), _stream()),
+               "allpairs_mlp_topk" + sfx)
     return idx, val, ex
 
 
@@ -746,10 +746,8 @@ def allpairs_mlp_topk_wide(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2
     MODE_HARD_ST.  rows = (r0, r1): those rows only (k and layout are theirs; AB, xp, deg stay every node's, G stays [N, N]).
     out = (idx, val, ex, w, rs): write into these tensors (tests: canaried buffers of any capacity >= layout.chunks; the spare chunks
     come back empty) instead of fresh ones.  prior = (rowptr, col, val): as allpairs_mlp_topk (dgg_allpairs_mlp_topk_wide_prior)."""
-    AB, xp, k = _chk(AB), _chk(xp), _chk(k)
-    N, h = xp.shape
-    hw = AB.shape[1] // 2
-    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    k = _chk(k)
+    (r0, r1), lead, sfx, pr = _apmlp_args(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2, act, noise_mode, G, seed, rows, prior)
     n = max(r1 - r0, 0)
     assert layout.rows == n and k.shape[0] == n, "allpairs_mlp_topk_wide: k and layout of the rows asked for"
     if out is None:
@@ -763,23 +761,9 @@ def allpairs_mlp_topk_wide(AB, xp, deg, ex_mode, t_ex, wdu, wdv, wex, b1, w2, b2
         idx, val, ex, w, rs = out
         C_ = idx.shape[0]
         assert C_ >= layout.chunks
-    ldG = 0
-    if G is not None:
-        G = _chk(G)
-        ldG = G.shape[-1]
-    o = lambda t_: None if t_ is None else _chk(t_)  # noqa: E731
-    if prior is not None:
-        prp, pci, pv = _prior_arrays(prior, N)
-        _lib.check(_lib.lib().dgg_allpairs_mlp_topk_wide_prior(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex),
-                                                               _ptr(o(wdu)), _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)),
-                                                               _ptr(_chk(b2)), act, noise_mode, _ptr(G), ldG, seed[0], seed[1], _ptr(k), mode,
-                                                               layout.maxm, _ptr(layout.cptr), C_, _ptr(idx), _ptr(val), _ptr(ex), _ptr(w),
-                                                               _ptr(rs), _ptr(prp), _ptr(pci), _ptr(pv), _stream()), "allpairs_mlp_topk_wide_prior")
-        return idx, val, ex, w, rs
-    _lib.check(_lib.lib().dgg_allpairs_mlp_topk_wide(_ptr(AB), _ptr(xp), N, h, hw, r0, r1, _ptr(o(deg)), ex_mode, float(t_ex), _ptr(o(wdu)),
-                                                     _ptr(o(wdv)), _ptr(o(wex)), _ptr(_chk(b1)), _ptr(_chk(w2)), _ptr(_chk(b2)), act, noise_mode,
-                                                     _ptr(G), ldG, seed[0], seed[1], _ptr(k), mode, layout.maxm, _ptr(layout.cptr), C_,
-                                                     _ptr(idx), _ptr(val), _ptr(ex), _ptr(w), _ptr(rs), _stream()), "allpairs_mlp_topk_wide")
+    _lib.check(getattr(_lib.lib(), "dgg_allpairs_mlp_topk_wide" + sfx)(*lead, _ptr(k), mode, layout.maxm, _ptr(layout.cptr), C_, _ptr(idx), _ptr(val),
+                                                                       _ptr(ex), _ptr(w), _ptr(rs), *map(_ptr, pr), _stream()),
+               "allpairs_mlp_topk_wide" + sfx)
     return idx, val, ex, w, rs
 
 

@@ -2,7 +2,7 @@
 """Times the wide-row form of the edge-MLP scorers on all-pairs candidates on one GPU (diagnostic): ops.allpairs_mlp_topk_wide and the
 autograd node on chunked rows.  Scorer u-v-deg, per-pair hash noise, h = hw = 64.
 
-    python tools/time_allpairs_mlp_wide.py [--part list|csr|passes ...] [--windows 7]
+    python tools/time_allpairs_mlp_wide.py [--part list|csr|passes|baseline ...] [--windows 7] [--baseline-lib PATH/libdgg_hip.so]
 
     list    N = 4096 and 20000, k ~ 30 (every row one chunk): the wide kernel against dgg_allpairs_mlp_topk (alone, and followed by
             softk_fwd, which the wide kernel fuses) on the same inputs -- the cost of the cascade and of two rows per wavefront
@@ -10,6 +10,10 @@ autograd node on chunked rows.  Scorer u-v-deg, per-pair hash noise, h = hw = 64
             this result without it: the CSR form on the complete pattern (_DGGScoresFn + ops.CsrSoftkFn: N^2-sized arrays)
     passes  N = 20000, k ~ 30 / 130 / 600: one sweep settles ops.APMLP_WIDE_REG_CHUNKS chunks of a row; time, sweeps, time per sweep
             relative to the one-chunk sweep
+    baseline  (with --baseline-lib: a second build of the library, for instance the parent commit's; tools/baseline_lib.py)
+            dgg_allpairs_mlp_topk_wide (u-v-deg) and dgg_allpairs_mlp_topk_wide_prior (u-v-A_uv, 4 random entries per row plus self loops)
+            of both builds at N = 20000 with k ~ 32 (one chunk) and ~ 130 (three chunks) and at N = 4096 with k ~ 600 (ten chunks: a
+            continuation sweep), outputs bit-equal before anything is timed; the verdict is baseline_lib.compare's
 
 Each figure is the median over `windows` timed windows (device events around `reps` back-to-back calls, reps chosen so that a window
 lasts about a quarter of a second), with the smallest and largest window next to it.  The variants of a part alternate window by
@@ -23,13 +27,17 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+import dgg_amd  # noqa: E402
 from dgg_amd import ops  # noqa: E402
+from baseline_lib import Baseline, compare, same_bits  # noqa: E402
 from dgg_amd.dgm import _DGGAllPairsMlpWideAdjFn, _DGGScoresFn  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--part", nargs="*", default=["list", "csr", "passes"], choices=["list", "csr", "passes"])
+ap.add_argument("--part", nargs="*", default=["list", "csr", "passes"], choices=["list", "csr", "passes", "baseline"])
 ap.add_argument("--windows", type=int, default=7)
+ap.add_argument("--baseline-lib", default=None)
 a = ap.parse_args()
+assert ("baseline" in a.part) == (a.baseline_lib is not None), "--part baseline and --baseline-lib go together"
 assert torch.cuda.is_available(), "time_allpairs_mlp_wide.py needs a GPU"
 dev = torch.device("cuda", 0)
 H = HW = 64
@@ -55,7 +63,8 @@ def reps_for(fn):
 
 
 def timed(paths, **tags):
-    """alternates the paths window by window -> {name: median ms}; prints one JSON line per path"""
+    """alternates the paths window by window -> {name: median ms}; prints one JSON line per path (with the verdict against its
+    "..., baseline build" twin, if it has one)"""
     reps = {name: reps_for(fn) for name, fn in paths.items()}
     times = {name: [] for name in paths}
     for _ in range(a.windows):
@@ -64,8 +73,9 @@ def timed(paths, **tags):
     med = {}
     for name, ts in times.items():
         med[name] = statistics.median(ts)
+        twin = times.get(name + ", baseline build")
         print(json.dumps(dict(tags, what=name, median_ms=round(med[name], 4), min_ms=round(min(ts), 4), max_ms=round(max(ts), 4),
-                              reps=reps[name], windows=a.windows)), flush=True)
+                              reps=reps[name], windows=a.windows, **(compare(ts, twin) if twin else {}))), flush=True)
     return med
 
 
@@ -170,3 +180,25 @@ if "passes" in a.part:
         m = timed({"wide": wide_call(t, k, lay)}, part="passes", N=N, k=what, chunks_per_row=lay.maxm, sweeps=sweeps)
         print(json.dumps(dict(part="passes", N=N, k=what, sweeps=sweeps, ms_per_sweep=round(m["wide"] / sweeps, 4),
                               per_sweep_over_one_chunk_sweep=round(m["wide"] / sweeps / one_chunk_ms[N], 3))), flush=True)
+
+if "baseline" in a.part:
+    base = Baseline(a.baseline_lib)
+    for N, what, lo, hi in ((20000, "~32", 27.0, 37.0), (20000, "~130", 120.0, 140.0), (4096, "~600", 590.0, 610.0)):
+        t = inputs(N)
+        g = torch.Generator().manual_seed(N + 1)
+        graph = torch.sparse_coo_tensor(torch.stack([torch.arange(N).repeat_interleave(4), torch.randint(0, N, (4 * N,), generator=g)]),
+                                        torch.ones(4 * N), (N, N)).coalesce().to(dev)
+        prior = dgg_amd.AllPairs.from_graph(graph, self_loops=True).prior_csr()[:3]
+        wex = (torch.randn(HW, generator=g) * 0.5).to(dev)
+        k = (lo + (hi - lo) * t["u"]).contiguous()
+        lay = ops.chunk_layout(k, ncols=N)
+
+        def uvauv():
+            return ops.allpairs_mlp_topk_wide(t["AB"], t["xp"], None, 1, 0.0, None, None, wex, t["eb1"], t["w2"], t["b2"], ops.ACT_LEAKY, k, lay,
+                                              ops.MODE_K_TIMES_EDGE_PROB, ops.NOISE_HASH, None, SEED, prior=prior)
+
+        paths = {"wide, u-v-deg": wide_call(t, k, lay), "wide, u-v-A_uv with the prior": uvauv}
+        for name in list(paths):
+            paths[name + ", baseline build"] = base.calls(paths[name])
+            assert same_bits(paths[name](), paths[name + ", baseline build"]()), f"the two builds disagree on {name}"
+        timed(paths, part="baseline", N=N, k=what, chunks_per_row=lay.maxm, sweeps=-(-lay.maxm // ops.APMLP_WIDE_REG_CHUNKS))

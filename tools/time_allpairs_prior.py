@@ -3,14 +3,15 @@
 (diagnostic, one GPU): h = hw = 64, per-pair hash noise, a prior of --per-row random entries per row plus self loops; the same kernel
 on an EMPTY prior (no tile ever holds an entry) is timed next to it: the difference is what the lookup costs.
 
-    python tools/time_allpairs_prior.py [N ...] [--hw 64] [--per-row 4] [--windows 7] [--baseline-lib PATH/libdgg_hip.so]
+    python tools/time_allpairs_prior.py [N ...] [--hw 64] [--per-row 4] [--windows 7] [--baseline-lib PATH/libdgg_hip.so] [--dist]
 
---baseline-lib: a second build of the library (for instance the parent commit's); its dgg_allpairs_mlp_topk is timed for u-v-deg in
-the same process, alternating with the others, so that "the u-v-deg kernel did not move" is read off one run under the same clocks.
+--baseline-lib: a second build of the library (for instance the parent commit's); its dgg_allpairs_mlp_topk (u-v-deg) and
+dgg_allpairs_mlp_topk_prior (u-v-A_uv with the prior) are timed in the same process, alternating with the others, after their outputs
+were found bit-equal to the tree's, so that "the kernels did not move" is read off one run under the same clocks (tools/baseline_lib.py).
+--dist: u-v-deg-dist (the distance extra) as well.
 Each figure is the median over `windows` timed windows (device events around `reps` back-to-back calls, a window lasts about a quarter
 of a second), with the smallest and largest window next to it: that spread is what a difference has to exceed."""
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -20,7 +21,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import dgg_amd  # noqa: E402
-from dgg_amd import _lib, ops  # noqa: E402
+from dgg_amd import ops  # noqa: E402
+from baseline_lib import Baseline, compare, same_bits  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("sizes", nargs="*", type=int, default=[100000])
@@ -28,15 +30,12 @@ ap.add_argument("--hw", type=int, default=64)
 ap.add_argument("--per-row", type=int, default=4)
 ap.add_argument("--windows", type=int, default=7)
 ap.add_argument("--baseline-lib", default=None)
+ap.add_argument("--dist", action="store_true")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "time_allpairs_prior.py needs a GPU"
 dev = torch.device("cuda", 0)
 hw = h = a.hw
-base = None
-if a.baseline_lib:
-    base = ctypes.CDLL(a.baseline_lib)
-    base.dgg_allpairs_mlp_topk.argtypes = _lib.PROTOTYPES["dgg_allpairs_mlp_topk"]
-    base.dgg_allpairs_mlp_topk.restype = ctypes.c_int
+base = Baseline(a.baseline_lib) if a.baseline_lib else None
 
 
 def window(fn, reps):
@@ -87,20 +86,19 @@ for N in a.sizes:
         return ops.allpairs_mlp_topk(AB, xp, None, 1, 0.0, None, None, wex, b1, w2, b2, ops.ACT_LEAKY, 64, ops.NOISE_HASH, None, (9, 4),
                                      out=(idx, val, ex), prior=empty)
 
+    def uvdist():
+        return ops.allpairs_mlp_topk(AB, xp, deg, 2, -1.0, wdu, wdv, wex, b1, w2, b2, ops.ACT_LEAKY, 64, ops.NOISE_HASH, None, (9, 4),
+                                     out=(idx, val, ex))
+
     paths = {"u-v-A_uv with the prior": uvauv, "u-v-A_uv, empty prior": uvauv_empty, "u-v-deg": uvdeg}
-    if base is not None:
-        p = ops._ptr
-        bi, bv = torch.empty_like(idx), torch.empty_like(val)
-
-        def uvdeg_base():
-            rc = base.dgg_allpairs_mlp_topk(p(AB), p(xp), N, h, hw, 0, N, p(deg), 0, 0.0, p(wdu), p(wdv), None, p(b1), p(w2), p(b2), ops.ACT_LEAKY,
-                                            ops.NOISE_HASH, None, 0, 9, 4, 64, p(bi), p(bv), None, ops._stream())
-            assert rc == 0
-
-        uvdeg()
-        uvdeg_base()
-        assert torch.equal(idx, bi) and torch.equal(val.view(torch.int32), bv.view(torch.int32)), "the two builds disagree on u-v-deg"
-        paths["u-v-deg, baseline build"] = uvdeg_base
+    if a.dist:
+        paths["u-v-deg-dist"] = uvdist
+    both = [name for name in paths if name != "u-v-A_uv, empty prior"] if base is not None else []
+    for name in both:
+        fn_base = base.calls(paths[name])
+        r_tree = tuple(None if t_ is None else t_.clone() for t_ in paths[name]())
+        assert same_bits(r_tree, fn_base()), f"the two builds disagree on {name}"
+        paths[name + ", baseline build"] = fn_base
     uvauv()
     torch.cuda.synchronize()
     kept_edges = int((ex != 0).sum())
@@ -112,10 +110,10 @@ for N in a.sizes:
     out = dict(N=N, hw=hw, h=h, noise="hash", prior_nnz=int(prior[1].shape[0]), kept_prior_edges=kept_edges, windows=a.windows)
     for name, ts in times.items():
         med = statistics.median(ts)
-        print(f"N={N:7d} hw={hw}  {name:26s} median {med:10.3f} ms  (windows {min(ts):.3f} .. {max(ts):.3f} ms, {reps[name]} calls each)", flush=True)
+        print(f"N={N:7d} hw={hw}  {name:41s} median {med:10.3f} ms  (windows {min(ts):.3f} .. {max(ts):.3f} ms, {reps[name]} calls each)", flush=True)
         out[name.replace(",", "").replace(" ", "_") + "_ms"] = dict(median=med, min=min(ts), max=max(ts), reps=reps[name])
     out["ratio_prior_over_empty_prior"] = statistics.median(times["u-v-A_uv with the prior"]) / statistics.median(times["u-v-A_uv, empty prior"])
     out["ratio_prior_over_uvdeg"] = statistics.median(times["u-v-A_uv with the prior"]) / statistics.median(times["u-v-deg"])
-    if base is not None:
-        out["ratio_uvdeg_over_baseline_build"] = statistics.median(times["u-v-deg"]) / statistics.median(times["u-v-deg, baseline build"])
+    for name in both:
+        out["vs_baseline_" + name.replace(" ", "_")] = compare(times[name], times[name + ", baseline build"])
     print(json.dumps(out), flush=True)
