@@ -514,7 +514,8 @@ class _FusedDGGConvFn(torch.autograd.Function):
 class _FusedDGGMlpConvFn(torch.autograd.Function):
     """_FusedDGGConvFn with an edge-MLP scorer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv; reference dgm.py:1628-1719) on edge-list
     candidates, or (u-v-deg, u-v-deg-dist, edge_conv; args.dgg_allpairs_mlp_fused = True) on all-pairs candidates: the scorer's terms arrive in the per-node / per-edge form of DGG_LearnableK_debug._edge_mlp_terms (sliced from the
-    reference's parameters by differentiable torch ops outside this node) and get their gradients from the same backward."""
+    reference's parameters by differentiable torch ops outside this node) and get their gradients from the same backward.
+    u-v-A_uv on all-pairs candidates that carry a prior (args.dgg_allpairs_prior_fused = True): sc_static["prior"] = the prior's CSR arrays."""
 
     @staticmethod
     def forward(ctx, x, deg, layer, sc_static, Wcat, wdu, wdv, wex, b1, w2, b2, *params):
@@ -716,8 +717,9 @@ class DGG_LearnableK_debug(nn.Module):
         reference's training scripts reads the class scores only, train_small_graphs.py:226-230), or None when this configuration
         is outside the fused step (the caller then runs the modules one after the other): scorer u-v-dist (any candidates) or an
         edge-MLP scorer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv, A_uv on edge-list candidates; u-v-deg, u-v-deg-dist, edge_conv on
-        all-pairs candidates as an opt-in, args.dgg_allpairs_mlp_fused = True -- on the 64-rank list or, with args.dgg_allpairs_mlp_rows =
-        "chunked", on chunked rows), k-net "x", soft
+        all-pairs candidates as an opt-in, args.dgg_allpairs_mlp_fused = True, and u-v-A_uv on all-pairs candidates that carry a prior
+        -- AllPairs(deg, prior=) -- as an opt-in of its own, args.dgg_allpairs_prior_fused = True -- on the 64-rank list or, with
+        args.dgg_allpairs_mlp_rows = "chunked", on chunked rows), k-net "x", soft
         k_times_edge_prob / k_only output, widths the partitioned backward covers, rows that fit the ELL width.
         want_norm: additionally return the NORMALISED adjacency as a differentiable EllAdjacency for the layers that read the same
         graph after this one (GCN_DGG's second layer): its gradient flows back into the generator through the same node.
@@ -775,17 +777,21 @@ class DGG_LearnableK_debug(nn.Module):
         a, h = self.args, self.latent_dim
         fin, fout = conv_weight.shape
         mlp_mode = self.edge_prob_net_mode in _EDGE_MLP_FUSED
+        # u-v-A_uv against a prior graph -- AllPairs(deg, prior=) -- has an opt-in of its own, args.dgg_allpairs_prior_fused = True
+        # (enough alone: it does not need dgg_allpairs_mlp_fused as well); the prior's CSR arrays are the scorer's per-pair input
+        prior_opt = bool(getattr(a, "dgg_allpairs_prior_fused", False)) and self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS_PRIOR
         clauses = (
             ("scorer outside u-v-dist / the edge-MLP family", self.edge_prob_net_mode != "u-v-dist" and not mlp_mode),
             # an edge-MLP scorer on all-pairs candidates enters the fused layer (and ShardedGCN_DGG) as an OPT-IN,
             # args.dgg_allpairs_mlp_fused = True: without it the forward keeps the separate modules it has always taken -- their bits,
             # their autograd edges (a differentiable unnorm_adj) and this clause in fused_fallback
             ("edge-MLP scorer on all-pairs candidates",
-             mlp_mode and isinstance(in_adj, AllPairs) and not getattr(a, "dgg_allpairs_mlp_fused", False)),
+             mlp_mode and isinstance(in_adj, AllPairs) and not (getattr(a, "dgg_allpairs_mlp_fused", False) or prior_opt)),
             # (all-pairs candidates without a prior have no stored values: u-v-A_uv / A_uv raise in forward(), where the separate modules
-            #  send them; with a prior -- AllPairs(deg, prior=) -- u-v-A_uv runs there, and stays outside the fused layer: a follow-up)
+            #  send them; with a prior -- AllPairs(deg, prior=) -- u-v-A_uv runs there, and enters the fused layer under its own opt-in)
             ("edge-MLP scorer on all-pairs candidates that reads the stored values of in_adj (u-v-A_uv / A_uv)",
-             mlp_mode and isinstance(in_adj, AllPairs) and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS),
+             mlp_mode and isinstance(in_adj, AllPairs) and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS
+             and not (prior_opt and in_adj.prior_csr() is not None)),
             # (dgg_allpairs_mlp_topk is built for these widths; edge_conv's hidden width is latent_dim / 2)
             ("edge-MLP scorer on all-pairs candidates: latent / hidden width outside {16, 32, 64, 128} (edge_conv: latent from 32)",
              mlp_mode and isinstance(in_adj, AllPairs) and (h not in (16, 32, 64, 128) or (self.edge_prob_net_mode == "edge_conv" and h == 16))),
@@ -807,9 +813,12 @@ class DGG_LearnableK_debug(nn.Module):
 
     def _fused_scorer(self, in_adj):
         """the edge-MLP scorer's parameters and per-edge inputs for the fused node, in the CSR order of the candidates -> (mlp, static).
-        All-pairs candidates (the scorers of _EDGE_MLP_ALLPAIRS) have no per-edge inputs and no pattern is read: erow = ex_in = None."""
+        All-pairs candidates (the scorers of _EDGE_MLP_ALLPAIRS) have no per-edge inputs and no pattern is read: erow = ex_in = None.
+        All-pairs candidates that carry a prior, scorer u-v-A_uv: static["prior"] = the prior's (rowptr, col, val), which the search looks a
+        pair's extra up in (ex_mode 1); still no per-edge inputs, and the prior's values are data -- they get no gradient."""
         h = self.latent_dim
         all_pairs = isinstance(in_adj, AllPairs)
+        prior = self._scorer_prior(in_adj.prior_csr()) if all_pairs else None
         avals = None if all_pairs else _cached("values_f32", in_adj, lambda: in_adj.coalesce().values().to(torch.float32).contiguous())
         if self.edge_prob_net_mode in ("edge_conv", "A_uv"):
             mlp, ex_in = self._edge_mlp_terms(avals)
@@ -824,7 +833,10 @@ class DGG_LearnableK_debug(nn.Module):
                        b2=self.edge_encode[2].bias, act=ops.ACT_LEAKY, ex_mode={"u-v-deg": 0, "u-v-A_uv": 1, "u-v-deg-dist": 2}[self.edge_prob_net_mode],
                        t_ex=-1.0 if self.edge_prob_net_mode == "u-v-deg-dist" else 0.0)
             ex_in = avals if self.edge_prob_net_mode == "u-v-A_uv" else None
-        return mlp, dict(erow=None if all_pairs else csr_pattern(in_adj)[2], ex_in=ex_in, ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], packed=packed)
+        static = dict(erow=None if all_pairs else csr_pattern(in_adj)[2], ex_in=ex_in, ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], packed=packed)
+        if prior is not None:
+            static["prior"] = prior
+        return mlp, static
 
     def _fused_configure(self, layer, x, cand, wide_state, mlp_mode):
         """sets the engine up for this forward: noise generator, selection mode, what rows wider than 64 ranks do, device flags

@@ -22,6 +22,10 @@ way to the per-pair hash of the same law, as on one GPU): every rank scores all 
 dgg_allpairs_mlp_topk, or of dgg_allpairs_mlp_topk_wide on chunked rows under args.dgg_allpairs_mlp_rows = "chunked", and the adjacency
 returned is the rank's rows with global columns (`layout` set for chunked rows).  The N^2 scoring is row-parallel, so this is the
 configuration a row shard divides best; no run on several GPUs has been timed.
+u-v-A_uv, which reads the input graph's stored values, runs the same way on all-pairs candidates that carry a prior graph --
+AllPairs(deg, prior=P) / AllPairs.from_graph -- under an opt-in of its own, args.dgg_allpairs_prior_fused = True (enough alone; without it,
+or without a prior, the wrapper raises as before; A_uv stays refused): every rank gets the whole prior, as it gets the whole prior_degree,
+and the row range of dgg_allpairs_mlp_topk_prior / dgg_allpairs_mlp_topk_wide_prior looks up the stored value of every pair of its rows.
 
 Edge-list rows wider than the 64-rank list whose learned degree needs more ranks than that leave the fused layer for the CSR form
 (DGG_LearnableK_debug._csr_soft_adjacency -> CsrAdjacency.normalize -> GCNConv on a CsrAdjacency), on one GPU and, as an OPT-IN, on a row

@@ -233,7 +233,9 @@ class ShardedDGGConv:
     layer's in one all-reduce.
     An edge-MLP scorer on ALL-PAIRS candidates (u-v-deg / u-v-deg-dist / edge_conv: they read the two end nodes and their prior degrees
     only) scores all N columns of the rank's rows in one kernel (allpairs_mlp_topk; chunked rows under wide_rows: allpairs_mlp_topk_wide)
-    under no / hash / symmetric hash noise keyed on the global pair; DESIGN.md has the step's kernel sequence."""
+    under no / hash / symmetric hash noise keyed on the global pair; DESIGN.md has the step's kernel sequence.  u-v-A_uv joins them when
+    the candidates carry a prior graph (scorer["prior"], replicated like the prior degrees): the same two kernels' _prior entries look a
+    pair's stored value up on the rank's row range and return it per kept slot, which is all the backward reads."""
 
     PARAM_KEYS = ("We", "be", "Wk", "bk", "W1", "b1", "Wmu", "bmu", "Wp", "bp", "Wc")
 
@@ -255,8 +257,9 @@ class ShardedDGGConv:
         # scorer: None = exp(t ||xp_i - xp_j||) (u-v-dist), or a dict with the edge-MLP scorer's terms in the per-node / per-edge form
         # of dgg_edge_mlp_fwd (reference dgm.py:1628-1719): Wcat [2hw,h], wdu / wdv / wex [hw] or None, b1 [hw], w2 [hw], b2 [1],
         # ex_mode, t_ex, act and, on edge-list candidates, erow int32 [E] and ex_in [E] or None (all-pairs candidates have no per-edge
-        # inputs: ex_mode 0 or 2, hw and h in {16, 32, 64, 128}).  backward() then also returns g["scorer"] = {Wcat, wdu, wdv, wex, b1,
-        # w2, b2} (the rest of the step is the same)
+        # inputs: ex_mode 0 or 2, or ex_mode 1 with prior = (rowptr int64 [N+1], col int32, val float32), the whole prior graph's CSR
+        # arrays, in which the search looks up the extra of a pair -- u-v-A_uv; hw and h in {16, 32, 64, 128}).  backward() then also
+        # returns g["scorer"] = {Wcat, wdu, wdv, wex, b1, w2, b2} (the rest of the step is the same; the prior's values get no gradient)
         self.scorer = None
         assert cand is None or noise_mode in (0, 2, 3), "edge-list candidates: noise_mode none / hash / symmetric hash"
         assert x_full is None or not x_grad, "replicated features are data: they cannot take a gradient"
@@ -599,15 +602,18 @@ class ShardedDGGConv:
         s["AB"] = AB = kern.linear_fwd(xp, sc["Wcat"], None, 0, 0)
         s["sdeg"] = sdeg = deg_full if sc["wdu"] is not None else None
         terms = (AB, xp, sdeg, sc["ex_mode"], sc["t_ex"], sc["wdu"], sc["wdv"], sc["wex"], sc["b1"], sc["w2"], sc["b2"], sc["act"])
+        # u-v-A_uv against a prior graph: the WHOLE graph's CSR arrays on every rank (the kernel looks up the pairs of its row range);
+        # handed on only when the scorer carries one -- the contract's entries, and a stand-in written to them, take no prior=
+        pk = {} if sc.get("prior") is None else {"prior": sc["prior"]}
         s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)) else None
         if lay is not None:                         # rows wider than 64 ranks: ceil(k_i + 8.5) + 1 ranks of every row, the ramp fused
-            got = kern.allpairs_mlp_topk_wide(*terms, k, lay, self.mode, nm, None, self.seed, rows=rows)
+            got = kern.allpairs_mlp_topk_wide(*terms, k, lay, self.mode, nm, None, self.seed, rows=rows, **pk)
             if got is None:
                 raise NotImplementedError("ShardedDGGConv: the kernel namespace has no allpairs_mlp_topk_wide (edge-MLP scorer, chunked rows)")
             idx, val, ex, w, rs_local = got
             s["ex"], s["eid"] = (None if ex is None else ex.reshape(-1)), None
             return idx, val, w, rs_local
-        got = kern.allpairs_mlp_topk(*terms, self.K, nm, None, self.seed, rows=rows)
+        got = kern.allpairs_mlp_topk(*terms, self.K, nm, None, self.seed, rows=rows, **pk)
         if got is None:
             raise NotImplementedError("ShardedDGGConv: the kernel namespace has no allpairs_mlp_topk (edge-MLP scorer on all-pairs candidates)")
         idx, val, ex = got
