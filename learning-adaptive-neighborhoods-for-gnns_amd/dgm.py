@@ -9,10 +9,12 @@ Parameters are created in the reference's order with the reference's layer types
 same 34 keys/shapes (reference checkpoints load with strict=True) and the same default initialisation under
 the same torch seed.  Parameters that the reference registers but never uses (t, k_W, ...) are kept for that reason only.
 
-Edge scorers: `u-v-dist` (all-pairs or edge-list candidates) and the edge-MLP family on edge-list candidates
-(`u-v-deg` -- the reference's default, train_small_graphs.py:184-191 -- `u-v-A_uv`, `u-v-deg-dist`, `edge_conv`, `A_uv`;
-reference dgm.py:1628-1725).
+Edge scorers: `u-v-dist` and the edge-MLP family (`u-v-deg` -- the reference's default, train_small_graphs.py:184-191 --
+`u-v-A_uv`, `u-v-deg-dist`, `edge_conv`, `A_uv`; reference dgm.py:1628-1725), on edge-list candidates or on all-pairs candidates
+(`u-v-A_uv`: all-pairs candidates that carry a prior graph; `A_uv`: edge lists only).  What a scorer is stands in ONE table, _SCORERS;
+which node and kernel a configuration runs, and what is refused, in the route table of DESIGN.md section 5.
 """
+import collections
 import math
 import weakref
 
@@ -23,7 +25,20 @@ from . import ops
 from .adjacency import AllPairs, CsrAdjacency, EllAdjacency, _cached, csr_candidates, csr_pattern, csr_pattern_rows
 from .parallel import edge_mlp_score_bwd, uvdist_score_bwd
 
-_EDGE_MLP_MODES = ("u-v-A_uv", "u-v-deg", "u-v-deg-dist", "edge_conv", "A_uv")
+# The edge-MLP scorers, one record per args.dgg_mode_edge_net.  extras: extra columns of edge_encode.0.weight
+# [h, 2h + extras] (None: parameters of its own); cols: which of them is (wdu, wdv, wex), counted from 2h; ex_mode, t_ex: the per-pair
+# extra (0 none, 1 a stored value, 2 exp(t_ex ||xp_u - xp_v||)); act: hidden activation; reads_adj: the extra is in_adj's stored value;
+# allpairs: runs on all-pairs candidates "yes" / "prior" (only AllPairs(deg, prior=)) / "no"; fused: forward_conv covers it;
+# hidden: hidden width from latent_dim (the all-pairs kernels are built for ops.KERNEL_WIDTHS)
+_Scorer = collections.namedtuple("_Scorer", "extras cols ex_mode t_ex act reads_adj allpairs fused hidden")
+_SCORERS = {
+    "u-v-deg":      _Scorer(2, (0, 1, None), 0, 0.0, ops.ACT_LEAKY, False, "yes", True, lambda h: h),        # dgm.py:1645-1670
+    "u-v-A_uv":     _Scorer(1, (None, None, 0), 1, 0.0, ops.ACT_LEAKY, True, "prior", True, lambda h: h),    # dgm.py:1628-1644
+    "u-v-deg-dist": _Scorer(3, (0, 1, 2), 2, -1.0, ops.ACT_LEAKY, False, "yes", True, lambda h: h),          # dgm.py:1671-1702
+    "edge_conv":    _Scorer(None, None, 0, 0.0, ops.ACT_NONE, False, "yes", True, lambda h: h // 2),         # dgm.py:1703-1719
+    "A_uv":         _Scorer(None, None, 1, 0.0, ops.ACT_NONE, True, "no", True, lambda h: 1),                # dgm.py:1720-1725
+}
+_EDGE_MLP_ALLPAIRS = tuple(m_ for m_, s_ in _SCORERS.items() if s_.allpairs == "yes")     # (named in the refusals' texts)
 
 
 def _capturing():
@@ -215,6 +230,11 @@ class _DGGSoftAdjFn(torch.autograd.Function):
 _SC_KEYS = ("Wcat", "wdu", "wdv", "wex", "b1", "w2", "b2")      # the edge-MLP scorer's terms, in the order the nodes take them
 
 
+def _sc_terms(mlp):
+    """the seven scorer tensors of _edge_mlp_terms / _fused_scorer in node order"""
+    return tuple(mlp[k_] for k_ in _SC_KEYS)
+
+
 def _mlp_score_bwd(ctx, terms, xp, AB, idx, eid, val, dval, ex, perturb, i_wcat, **kw):
     """edge-MLP scorer backward of the three nodes below from d loss / d score (parallel.edge_mlp_score_bwd) -> dxp without the distance
     term, dex, the gradients of the scorer's terms in node order (Wcat's only if input `i_wcat` needs one).  terms = the saved (Wcat,
@@ -388,9 +408,6 @@ class _DGGScoresFn(torch.autograd.Function):
 
 
 _PAD_CACHE = {}
-_EDGE_MLP_FUSED = ("u-v-deg", "u-v-A_uv", "u-v-deg-dist", "edge_conv", "A_uv")     # edge-MLP scorers the fused layer covers
-_EDGE_MLP_ALLPAIRS = ("u-v-deg", "u-v-deg-dist", "edge_conv")     # ... that read the end nodes and their degrees only: all-pairs candidates
-_EDGE_MLP_ALLPAIRS_PRIOR = ("u-v-A_uv",)     # ... that read the input graph's values: all-pairs candidates that carry a prior (AllPairs(deg, prior=))
 
 
 def _pad_features(x, params, keys):
@@ -672,10 +689,7 @@ class DGG_LearnableK_debug(nn.Module):
         st = self.__dict__.setdefault("_asym_state", {"n": 0, "slow": False, "probe": None})
         every = max(1, int(getattr(self.args, "dgg_pilot_every", 16)))
         if st["n"] % every == 0 and not _capturing():
-            with torch.no_grad():
-                xp = ops.linear_fwd(x.detach(), self.node_encode_for_edges[0].weight.detach(), self.node_encode_for_edges[0].bias.detach(),
-                                    ops.ACT_LEAKY)
-                pr = ops.ranked_probe(xp, None, ops.T_DIST, seed, stride=max(1, N // 1024), max_blocks=64)
+            pr = self._pilot(x, seed, 64)
             est = ops.ranked_cost_estimate(pr, N)
             slow = est > float(getattr(self.args, "dgg_ranked_warn_us", 5000.0))
             if slow and not st["slow"]:
@@ -688,6 +702,13 @@ class DGG_LearnableK_debug(nn.Module):
             st.update(slow=slow, probe=dict(pr, ranked_us_estimate=est))
         st["n"] += 1
         return ops.NOISE_RANKED
+
+    def _pilot(self, x, seed, max_blocks):
+        """the ranked search walked over ~1000 sampled rows with a budget of `max_blocks` blocks (one small launch, one readback)"""
+        with torch.no_grad():
+            We, be = self.node_encode_for_edges[0].weight.detach(), self.node_encode_for_edges[0].bias.detach()
+            return ops.ranked_probe(ops.linear_fwd(x.detach(), We, be, ops.ACT_LEAKY), None, ops.T_DIST, seed,
+                                    stride=max(1, x.shape[0] // 1024), max_blocks=max_blocks)
 
     def _hash_spread_now(self, x, seed):
         """True while the latents of this module are SPREAD over several noise scales -- the regime in which the 64-rank entry of the per-pair
@@ -702,10 +723,7 @@ class DGG_LearnableK_debug(nn.Module):
         st = self.__dict__.setdefault("_hash_state", {"n": 0, "spread": False})
         every = max(1, int(getattr(self.args, "dgg_pilot_every", 16)))
         if st["n"] % every == 0 and not _capturing():
-            with torch.no_grad():
-                xp = ops.linear_fwd(x.detach(), self.node_encode_for_edges[0].weight.detach(), self.node_encode_for_edges[0].bias.detach(),
-                                    ops.ACT_LEAKY)
-                pr = ops.ranked_probe(xp, None, ops.T_DIST, seed if seed is not None else (0, 0), stride=max(1, N // 1024), max_blocks=16)
+            pr = self._pilot(x, seed if seed is not None else (0, 0), 16)
             st["spread"] = pr["blocks_per_row"] > 8.0
             st["blocks"] = pr["blocks_per_row"]
         st["n"] += 1
@@ -715,17 +733,12 @@ class DGG_LearnableK_debug(nn.Module):
         """`GCNConv(x, normalize_adj(self(x, in_adj)))` with conv_weight = GCNConv.W [in, out] as one fused autograd node
         (_FusedDGGConvFn) -> (Z, unnormalised EllAdjacency, DETACHED: its values carry no autograd edge -- the loss of the
         reference's training scripts reads the class scores only, train_small_graphs.py:226-230), or None when this configuration
-        is outside the fused step (the caller then runs the modules one after the other): scorer u-v-dist (any candidates) or an
-        edge-MLP scorer (u-v-deg, u-v-A_uv, u-v-deg-dist, edge_conv, A_uv on edge-list candidates; u-v-deg, u-v-deg-dist, edge_conv on
-        all-pairs candidates as an opt-in, args.dgg_allpairs_mlp_fused = True, and u-v-A_uv on all-pairs candidates that carry a prior
-        -- AllPairs(deg, prior=) -- as an opt-in of its own, args.dgg_allpairs_prior_fused = True -- on the 64-rank list or, with
-        args.dgg_allpairs_mlp_rows = "chunked", on chunked rows), k-net "x", soft
-        k_times_edge_prob / k_only output, widths the partitioned backward covers, rows that fit the ELL width.
+        is outside the fused step (the caller then runs the modules one after the other).  What the step covers, under which opt-in,
+        and the clause every other configuration is counted under: _fused_outside and the route table of DESIGN.md section 5.
         want_norm: additionally return the NORMALISED adjacency as a differentiable EllAdjacency for the layers that read the same
         graph after this one (GCN_DGG's second layer): its gradient flows back into the generator through the same node.
-        The steps: _fused_outside (configurations the node does not cover) -> candidates -> _fused_scorer (edge-MLP terms) ->
-        _fused_configure (noise generator, what rows wider than 64 ranks do, flags) -> the node -> _fused_result (what the forward's
-        learned degrees decide after the fact, the returned adjacencies)."""
+        The steps: _fused_outside -> candidates -> _fused_scorer (edge-MLP terms) -> _fused_configure (noise generator, what rows wider
+        than 64 ranks do, flags) -> the node -> _fused_result (what the learned degrees decide after the fact, the returned adjacencies)."""
         return self._forward_conv(x, in_adj, conv_weight, want_norm)
 
     def _forward_conv(self, x, in_adj, conv_weight, want_norm, engine=None):
@@ -735,21 +748,15 @@ class DGG_LearnableK_debug(nn.Module):
         why = self._fused_outside(x, in_adj, conv_weight)
         if why is not None:
             return self._fused_fallback(why)
-        a, N = self.args, x.shape[0]
-        mlp_mode = self.edge_prob_net_mode in _EDGE_MLP_FUSED
-        wide_state = None
-        if isinstance(in_adj, AllPairs):
-            cand, deg, rowptr = None, in_adj.prior_degree, None
+        N = x.shape[0]
+        mlp_mode, wide_state = getattr(self._scorer(), "fused", False), None
+        in_adj, cand, deg, _, _, _ = self._candidates(in_adj)
+        if cand is None:
             # (args.dgg_wide_rows is u-v-dist's: the edge-MLP scorers have args.dgg_allpairs_mlp_rows, and no CSR form on all pairs)
-            if not mlp_mode and (self.__dict__.get("_ap_wide", {}).get("on") or (getattr(a, "dgg_wide_rows", "auto") == "csr" and
-                                                                                 N <= int(getattr(a, "dgg_allpairs_csr_max", 8192)))):
+            if not mlp_mode and (self.__dict__.get("_ap_wide", {}).get("on") or self._allpairs_csr_plan(N) == "csr"):
                 return None                                   # (policy "csr": every column ranked, the modules' CSR form)
         else:
-            if isinstance(in_adj, EllAdjacency):
-                in_adj = in_adj.to_sparse().detach()
-            rowptr, col, deg = csr_candidates(in_adj)
-            cand = (rowptr, col)
-            wide_state = self._wide_rows_state(in_adj, rowptr)
+            wide_state = self._wide_rows_state(in_adj, cand[0])
             if wide_state is True:                            # (known before any kernel runs: this graph takes the CSR form -- no discarded forward)
                 return self._fused_fallback("rows wider than the list with learned degrees beyond it (CSR form)")
         mlp, sc_static = self._fused_scorer(in_adj) if mlp_mode else (None, None)
@@ -764,11 +771,10 @@ class DGG_LearnableK_debug(nn.Module):
         # no backward can follow (torch.no_grad(), frozen parameters): the partition's sort -- read by the backward only -- is skipped
         layer.want_backward = ops.backward_will_follow(x, *params, *([mlp["Wcat"], mlp["b1"], mlp["w2"], mlp["b2"]] if mlp_mode else []))
         if mlp_mode:
-            Z, ahat = _FusedDGGMlpConvFn.apply(x, deg, layer, sc_static, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"],
-                                               mlp["w2"], mlp["b2"], *params)
+            Z, ahat = _FusedDGGMlpConvFn.apply(x, deg, layer, sc_static, *_sc_terms(mlp), *params)
         else:
             Z, ahat = _FusedDGGConvFn.apply(x, deg, layer, *params)       # (ops.ChunkCapacityError: a learned degree is NaN)
-        return self._fused_result(layer, Z, ahat, in_adj, cand, rowptr, noise_mode, chunk_active, mlp_mode, want_norm)
+        return self._fused_result(layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm)
 
     def _fused_outside(self, x, in_adj, conv_weight):
         """-> the reason this configuration is outside the fused layer, or None.  Which clause sends a forward to the separate modules
@@ -776,25 +782,22 @@ class DGG_LearnableK_debug(nn.Module):
         are ~1.7x slower at Pubmed size, and a silent fall-back looks like a performance bug of the fused layer"""
         a, h = self.args, self.latent_dim
         fin, fout = conv_weight.shape
-        mlp_mode = self.edge_prob_net_mode in _EDGE_MLP_FUSED
-        # u-v-A_uv against a prior graph -- AllPairs(deg, prior=) -- has an opt-in of its own, args.dgg_allpairs_prior_fused = True
-        # (enough alone: it does not need dgg_allpairs_mlp_fused as well); the prior's CSR arrays are the scorer's per-pair input
-        prior_opt = bool(getattr(a, "dgg_allpairs_prior_fused", False)) and self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS_PRIOR
+        sc = self._scorer()
+        mlp_mode = getattr(sc, "fused", False)
+        ap_mlp = mlp_mode and isinstance(in_adj, AllPairs)
+        runs, widths_ok = self._allpairs_mlp_ok(in_adj.prior_csr()) if ap_mlp else (True, True)
+        # (u-v-A_uv against a prior graph has an opt-in of its own, enough alone; the prior's CSR arrays are the scorer's per-pair input)
+        prior_opt = bool(getattr(a, "dgg_allpairs_prior_fused", False)) and mlp_mode and sc.allpairs == "prior"
         clauses = (
             ("scorer outside u-v-dist / the edge-MLP family", self.edge_prob_net_mode != "u-v-dist" and not mlp_mode),
-            # an edge-MLP scorer on all-pairs candidates enters the fused layer (and ShardedGCN_DGG) as an OPT-IN,
-            # args.dgg_allpairs_mlp_fused = True: without it the forward keeps the separate modules it has always taken -- their bits,
-            # their autograd edges (a differentiable unnorm_adj) and this clause in fused_fallback
-            ("edge-MLP scorer on all-pairs candidates",
-             mlp_mode and isinstance(in_adj, AllPairs) and not (getattr(a, "dgg_allpairs_mlp_fused", False) or prior_opt)),
-            # (all-pairs candidates without a prior have no stored values: u-v-A_uv / A_uv raise in forward(), where the separate modules
-            #  send them; with a prior -- AllPairs(deg, prior=) -- u-v-A_uv runs there, and enters the fused layer under its own opt-in)
+            # (an OPT-IN, args.dgg_allpairs_mlp_fused = True: without it the forward keeps the separate modules it has always taken --
+            #  their bits, their autograd edges (a differentiable unnorm_adj) and this clause in fused_fallback)
+            ("edge-MLP scorer on all-pairs candidates", ap_mlp and not (getattr(a, "dgg_allpairs_mlp_fused", False) or prior_opt)),
+            # (this clause and the next: the two answers of _allpairs_mlp_ok, which forward() raises on -- _check_all_pairs)
             ("edge-MLP scorer on all-pairs candidates that reads the stored values of in_adj (u-v-A_uv / A_uv)",
-             mlp_mode and isinstance(in_adj, AllPairs) and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS
-             and not (prior_opt and in_adj.prior_csr() is not None)),
-            # (dgg_allpairs_mlp_topk is built for these widths; edge_conv's hidden width is latent_dim / 2)
+             ap_mlp and not (runs and (sc.allpairs == "yes" or prior_opt))),
             ("edge-MLP scorer on all-pairs candidates: latent / hidden width outside {16, 32, 64, 128} (edge_conv: latent from 32)",
-             mlp_mode and isinstance(in_adj, AllPairs) and (h not in (16, 32, 64, 128) or (self.edge_prob_net_mode == "edge_conv" and h == 16))),
+             ap_mlp and not widths_ok),
             ("k-net mode other than 'x'", self.k_net_mode != "x"),
             ("k-select mode other than k_times_edge_prob / k_only", self.k_select_mode not in ("k_times_edge_prob", "k_only")),
             ("dgg_hard", bool(self.hard)),
@@ -803,8 +806,8 @@ class DGG_LearnableK_debug(nn.Module):
             ("explicit noise tensor", self._explicit_noise is not None),
             ("args.dgg_fused_layer = False", not getattr(a, "dgg_fused_layer", True)),
             ("input not on the GPU", not x.is_cuda),
-            ("latent width outside {16, 32, 64, 128}", h not in (16, 32, 64, 128) or h not in ops.KNET_MFMA_WIDTHS),
-            ("conv width outside {16, 32, 64, 128}", fout not in (16, 32, 64, 128)),
+            ("latent width outside {16, 32, 64, 128}", h not in ops.KERNEL_WIDTHS or h not in ops.KNET_MFMA_WIDTHS),
+            ("conv width outside {16, 32, 64, 128}", fout not in ops.CONV_BWD_WIDTHS),
             ("conv wider than its input (fout > fin)", fout > fin),
             ("ell_width other than 64", self.ell_width != 64),
             ("input dtype other than float32", x.dtype != torch.float32),
@@ -813,26 +816,21 @@ class DGG_LearnableK_debug(nn.Module):
 
     def _fused_scorer(self, in_adj):
         """the edge-MLP scorer's parameters and per-edge inputs for the fused node, in the CSR order of the candidates -> (mlp, static).
-        All-pairs candidates (the scorers of _EDGE_MLP_ALLPAIRS) have no per-edge inputs and no pattern is read: erow = ex_in = None.
+        All-pairs candidates have no per-edge inputs and no pattern is read: erow = ex_in = None.
         All-pairs candidates that carry a prior, scorer u-v-A_uv: static["prior"] = the prior's (rowptr, col, val), which the search looks a
         pair's extra up in (ex_mode 1); still no per-edge inputs, and the prior's values are data -- they get no gradient."""
-        h = self.latent_dim
+        h, sc = self.latent_dim, self._scorer()
         all_pairs = isinstance(in_adj, AllPairs)
         prior = self._scorer_prior(in_adj.prior_csr()) if all_pairs else None
         avals = None if all_pairs else _cached("values_f32", in_adj, lambda: in_adj.coalesce().values().to(torch.float32).contiguous())
-        if self.edge_prob_net_mode in ("edge_conv", "A_uv"):
+        if sc.extras is None:
             mlp, ex_in = self._edge_mlp_terms(avals)
             packed = None
         else:                                                 # edge_encode.0.weight goes into the node whole (sliced inside it)
-            need = {"u-v-deg": 2, "u-v-A_uv": 1, "u-v-deg-dist": 3}[self.edge_prob_net_mode]
-            W0 = self.edge_encode[0].weight
-            assert W0.shape[1] == 2 * h + need, f"edge mode {self.edge_prob_net_mode!r} needs extra_edge_dim={need} (edge_encode.0 is {tuple(W0.shape)})"
-            cols = {"u-v-deg": (2 * h, 2 * h + 1, None), "u-v-A_uv": (None, None, 2 * h), "u-v-deg-dist": (2 * h, 2 * h + 1, 2 * h + 2)}
-            packed = (h, cols[self.edge_prob_net_mode])
-            mlp = dict(Wcat=W0, wdu=None, wdv=None, wex=None, b1=self.edge_encode[0].bias, w2=self.edge_encode[2].weight,
-                       b2=self.edge_encode[2].bias, act=ops.ACT_LEAKY, ex_mode={"u-v-deg": 0, "u-v-A_uv": 1, "u-v-deg-dist": 2}[self.edge_prob_net_mode],
-                       t_ex=-1.0 if self.edge_prob_net_mode == "u-v-deg-dist" else 0.0)
-            ex_in = avals if self.edge_prob_net_mode == "u-v-A_uv" else None
+            packed = (h, tuple(None if c_ is None else 2 * h + c_ for c_ in sc.cols))
+            mlp = dict(Wcat=self._edge_encode_w0(sc), wdu=None, wdv=None, wex=None, b1=self.edge_encode[0].bias, w2=self.edge_encode[2].weight,
+                       b2=self.edge_encode[2].bias, act=sc.act, ex_mode=sc.ex_mode, t_ex=sc.t_ex)
+            ex_in = avals if sc.reads_adj else None
         static = dict(erow=None if all_pairs else csr_pattern(in_adj)[2], ex_in=ex_in, ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], packed=packed)
         if prior is not None:
             static["prior"] = prior
@@ -842,20 +840,15 @@ class DGG_LearnableK_debug(nn.Module):
         """sets the engine up for this forward: noise generator, selection mode, what rows wider than 64 ranks do, device flags
         -> (noise_mode, chunk_active = this forward reads its chunk layout back)"""
         a, N = self.args, x.shape[0]
-        noise_mode, _, seed = self._noise_cfg()
         ap_mlp = cand is None and mlp_mode                    # edge-MLP scorer on all-pairs candidates: every pair is scored, as on edge lists
-        if cand is None and noise_mode == ops.NOISE_RANKED and not ap_mlp:
-            noise_mode = self._asym_generator_now(x, seed)
-        elif cand is not None or ap_mlp:
-            noise_mode = {ops.NOISE_RANKED: ops.NOISE_HASH, ops.NOISE_RANKED_SYM: ops.NOISE_HASH_SYM}.get(noise_mode, noise_mode)
+        noise_mode, _, seed = self._noise_now(x, cand is None, ap_mlp)
         mode = ops.MODE_K_TIMES_EDGE_PROB if self.k_select_mode == "k_times_edge_prob" else ops.MODE_K_ONLY
         layer.cand, layer.noise_mode, layer.seed, layer.mode, layer.scorer = cand, noise_mode, seed, mode, None
         layer.sym_fallback, layer.sym_hash = getattr(a, "dgg_sym_generator", "auto") != "ranked", False
         if ap_mlp:
             # none of the ranked generators' pilots and fallbacks applies; rows wider than the list under the scorers' own opt-in
             # (args.dgg_allpairs_mlp_rows = "chunked"; a hipGraph capture keeps the list and its enforced bound: nothing can be read back)
-            layer.sym_fallback, layer.force_chunked, layer.tight_bound = False, False, "off"
-            layer.x_grad = bool(x.requires_grad)
+            layer.sym_fallback, layer.force_chunked, layer.tight_bound, layer.x_grad = False, False, "off", bool(x.requires_grad)
             chunked = self._allpairs_mlp_chunked() and not _capturing()
             layer.wide_rows, layer.wide_cap = ("auto" if chunked else "off"), None
             return noise_mode, chunked
@@ -870,8 +863,7 @@ class DGG_LearnableK_debug(nn.Module):
         # all-pairs rows wider than the 64-rank list (learned degrees k_i + 9.5 > 64): chunked rows inside the engine, from the forward
         # that first needs them (one readback of the chunk count per forward; a hipGraph capture replays the last eager layout)
         chunked = cand is None and self._chunk_policy(noise_mode)
-        layer.wide_rows = "auto" if chunked else "off"
-        layer.wide_cap = None
+        layer.wide_rows, layer.wide_cap = ("auto" if chunked else "off"), None
         if chunked and _capturing():
             # nothing can be read back under capture: the layout of the last eager forward on this module, with some slack, becomes a
             # FIXED capacity whose overflow flags check_ell_bound() reads; no wide row then: the list, with its enforced bound
@@ -889,7 +881,7 @@ class DGG_LearnableK_debug(nn.Module):
             layer.overflow = flag
         return noise_mode, chunked and layer.wide_rows == "auto" and layer.wide_cap is None
 
-    def _fused_result(self, layer, Z, ahat, in_adj, cand, rowptr, noise_mode, chunk_active, mlp_mode, want_norm):
+    def _fused_result(self, layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm):
         """after the node ran: generator status, what this forward's learned degrees decide (CSR form from here on / overflow flags),
         and the returned adjacencies"""
         st, N = layer.saved, layer.N
@@ -900,7 +892,7 @@ class DGG_LearnableK_debug(nn.Module):
         if st.get("partp") is None:                           # (shape outside the partitioned backward: the separate modules)
             return self._fused_fallback("shape outside the partitioned backward")
         k = st["k"]
-        if cand is not None and self._wide_rows(in_adj, rowptr, k, layer):
+        if cand is not None and self._wide_rows(in_adj, cand[0], k, layer):
             # rows wider than the ELL with learned degrees beyond it: the CSR form from here on (this forward is discarded, once per graph)
             if not mlp_mode and "_overflow_scratch" in self.__dict__:
                 self._overflow_scratch.zero_()
@@ -915,7 +907,7 @@ class DGG_LearnableK_debug(nn.Module):
         elif mlp_mode and cand is not None:
             ent = self.__dict__.get("_wide_cache", {}).get(id(in_adj))
             if not (ent is not None and ent[0]() is in_adj and ent[1] <= self.ell_width):     # (no row can outgrow the list otherwise)
-                self._track_overflow(k, self._row_lens(rowptr, layer))
+                self._track_overflow(k, self._row_lens(cand[0], layer))
         elif __import__("os").environ.get("DGG_STRICT_BOUND") == "1":
             self.check_ell_bound()
         unnorm = EllAdjacency(st["idx"], st["w"], N, rs=st["rs"], k=k, score=st["val"], owner=self, layout=lay)
@@ -978,28 +970,32 @@ class DGG_LearnableK_debug(nn.Module):
         policy = getattr(self.args, "dgg_wide_rows", "auto")
         return (policy in ("auto", "chunked") and noise_mode in (ops.NOISE_NONE, ops.NOISE_HASH, ops.NOISE_HASH_SYM, ops.NOISE_RANKED, ops.NOISE_RANKED_SYM)
                 and self.ell_width == 64
-                and self.latent_dim in (16, 32, 64, 128) and self.edge_prob_net_mode == "u-v-dist")
+                and self.latent_dim in ops.KERNEL_WIDTHS and self.edge_prob_net_mode == "u-v-dist")
 
     def wide_row_plan(self, N, all_pairs, noise_mode):
         """What rows that need more than 64 ranks do for a graph of N nodes under args.dgg_wide_rows -- the ONE summary of the policy
         (the predicates the forwards use: _chunk_policy, _wide_rows_state, _allpairs_wide):
           "chunked"          all-pairs candidates: ceil(k_i + 8.5) + 1 ranks of every row in chunks of 64, any width (auto / chunked;
-                             the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv: with args.dgg_allpairs_mlp_rows = "chunked",
-                             whatever args.dgg_wide_rows says -- except inside a hipGraph capture, where nothing can be read back:
+                             the edge-MLP scorers: with args.dgg_allpairs_mlp_rows = "chunked", whatever args.dgg_wide_rows says --
                              a captured forward keeps the list and its enforced bound although the answer here is "chunked")
           "csr"              the CSR form of select_top_k from the first forward (csr)
           "csr_when_needed"  the CSR form from the forward whose learned degrees first need it, and from then on (auto on edge lists
                              and for explicit noise tensors on small all-pairs graphs; csr_auto)
           "list"             64 ranks per row, the bound enforced by check_ell_bound (ell; graphs beyond dgg_allpairs_csr_max without a
-                             chunked form; the edge-MLP scorers u-v-deg / u-v-deg-dist / edge_conv on all-pairs candidates unless
-                             args.dgg_allpairs_mlp_rows = "chunked")"""
+                             chunked form; the edge-MLP scorers on all-pairs candidates unless args.dgg_allpairs_mlp_rows = "chunked")
+        Which node runs each row form: the route table of DESIGN.md section 5."""
         policy = getattr(self.args, "dgg_wide_rows", "auto")
         if not all_pairs:
             return {"ell": "list", "csr": "csr"}.get(policy, "csr_when_needed")
         if self._chunk_policy(noise_mode):
             return "chunked"
-        if self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS + _EDGE_MLP_ALLPAIRS_PRIOR:     # (the edge-MLP scorers on all-pairs candidates -- u-v-A_uv: with a prior -- have an opt-in of their own)
+        if getattr(self._scorer(), "allpairs", "no") != "no":     # (the edge-MLP scorers on all-pairs candidates -- u-v-A_uv: with a prior -- have an opt-in of their own)
             return "chunked" if self._allpairs_mlp_chunked() else "list"
+        return self._allpairs_csr_plan(N)
+
+    def _allpairs_csr_plan(self, N):
+        """wide_row_plan for all-pairs candidates that have no chunked form (u-v-dist): "list" / "csr" / "csr_when_needed" """
+        policy = getattr(self.args, "dgg_wide_rows", "auto")
         if policy in ("ell", "chunked") or N > int(getattr(self.args, "dgg_allpairs_csr_max", 8192)):
             return "list"
         return "csr" if policy == "csr" else "csr_when_needed"
@@ -1019,12 +1015,12 @@ class DGG_LearnableK_debug(nn.Module):
         return rows == "chunked"
 
     @staticmethod
-    def _log_first_k_chunked(writer, epoch, cfg, w, val, lay):
-        """the two scalars the reference logs from inside the DGG (dgm.py:1259-1261), on chunked rows"""
+    def _log_first_k(writer, epoch, cfg, w, val, lay=None):
+        """the two scalars the reference logs from inside the DGG (dgm.py:1259-1261); lay: on chunked rows"""
         if writer is None:
             return
         f = w.detach() if (cfg["mode"] == ops.MODE_K_ONLY or "fwd_mode" in cfg) else (w.detach() / val.clamp(min=1e-30))
-        fs = torch.zeros(lay.rows, device=w.device).index_add_(0, lay.cnode.long(), f.sum(-1))
+        fs = f.sum(-1) if lay is None else torch.zeros(lay.rows, device=w.device).index_add_(0, lay.cnode.long(), f.sum(-1))
         writer.add_scalar("values/first_k_std", fs.std(), epoch)
         writer.add_scalar("values/first_k_mean", fs.mean(), epoch)
 
@@ -1108,15 +1104,12 @@ class DGG_LearnableK_debug(nn.Module):
         and training moves it past that within a few steps (test_learned_degrees_of_a_trained_model_and_the_all_pairs_list).  Graphs
         of at most `args.dgg_allpairs_csr_max` (8192) nodes -- the sizes at which the reference's dense [N,N] formulation runs at
         all -- then take select_top_k on the COMPLETE candidate pattern in CSR form (every column ranked, any degree: N^2 entries,
-        a few milliseconds at N = 3000), as rows wider than the list do for edge-list candidates.  args.dgg_wide_rows: "auto"
-        (default: from the forward in which some k_i + 8.5 first exceeds the width, and from then on -- one flag read back per forward
-        while the list is still in use; a hipGraph capture replays the last decision), "csr" (always), "ell" (never: the bound is
-        enforced by check_ell_bound).  Larger graphs keep the list and the enforced bound."""
-        policy = getattr(self.args, "dgg_wide_rows", "auto")
-        if policy in ("ell", "chunked") or N > int(getattr(self.args, "dgg_allpairs_csr_max", 8192)):
-            return False
-        if policy == "csr":
-            return True
+        a few milliseconds at N = 3000), as rows wider than the list do for edge-list candidates.  _allpairs_csr_plan: "csr" always,
+        "list" never (the bound is enforced by check_ell_bound), "csr_when_needed" from the forward in which some k_i + 8.5 first exceeds
+        the width, and from then on -- one flag read back per forward while the list is in use; a capture replays the last decision."""
+        plan = self._allpairs_csr_plan(N)
+        if plan != "csr_when_needed":
+            return plan == "csr"
         st = self.__dict__.setdefault("_ap_wide", {"on": False})
         if not st["on"] and not _capturing():
             st["on"] = bool((k.detach() + 8.5 > float(self.ell_width)).any().item())
@@ -1129,22 +1122,8 @@ class DGG_LearnableK_debug(nn.Module):
         rows = (r0, r1) (dgg_amd.distributed.ShardedGCN_DGG): rows [r0, r1) of in_adj only, k their learned degrees [r1 - r0]; x and the
         projection stay the whole graph's -> the CsrAdjacency of those rows (global columns, the bits of the whole graph's rows), whose
         backward leaves the shard's share of every gradient."""
-        if pattern is None:
-            in_adj = in_adj.coalesce()
-            pattern = csr_pattern(in_adj)
-            _, _, deg = csr_candidates(in_adj)
-        if rows is not None:
-            assert in_adj is not None and G is None and not self.hard, "a row shard: edge-list candidates, counter-based noise, soft output"
-            pattern, (e0, e1) = csr_pattern_rows(in_adj, rows)
-        We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
-        cfg = dict(cand=pattern, t=ops.T_DIST, rows=rows)
-        if self.edge_prob_net_mode == "u-v-dist":
-            p = _DGGScoresFn.apply(x, None, None, We, be, None, None, None, None, None, None, None, cfg)
-        else:
-            avals = in_adj.values().to(torch.float32)
-            mlp, ex_in = self._edge_mlp_terms(avals if rows is None else avals[e0:e1])
-            cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
-            p = _DGGScoresFn.apply(x, deg, ex_in, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"], mlp["w2"], mlp["b2"], cfg)
+        assert rows is None or (in_adj is not None and G is None and not self.hard), "a row shard: edge-list candidates, counter-based noise, soft output"
+        p, pattern = self._edge_probs(x, in_adj, pattern, deg, rows)
         if rows is not None:
             w = ops.CsrSoftkRowsFn.apply(p, k, pattern[0], pattern[1], rows, x.shape[0], noise_mode, seed, mode)
             return CsrAdjacency(pattern[0], pattern[1], pattern[2], w, x.shape[0], k=k.detach(), row0=rows[0], n_rows=rows[1] - rows[0])
@@ -1172,40 +1151,46 @@ class DGG_LearnableK_debug(nn.Module):
         # the ranked generator's row search is written for the full 64-wide list
         return (ops.NOISE_RANKED if self.ell_width == 64 else ops.NOISE_HASH), None, seed
 
-    def _edge_mlp_terms(self, avals):
-        """The reference's scorer parameters in the per-node / per-edge form of dgg_edge_mlp_fwd (differentiable slicing).
+    def _noise_now(self, x, all_pairs, every_pair=False, literal=False):
+        """_noise_cfg() as the search of THIS forward runs it -> (noise_mode, G, seed).  The ranked generators serve the early-stopping
+        search of all-pairs u-v-dist only: wherever every candidate is scored -- edge lists, every_pair = an edge-MLP scorer on all-pairs
+        candidates, the full ranking of literal dgg_hard -- the per-pair hash of the same law takes their place (ops.hash_noise_mode, the
+        one mapping).  The ranked asymmetric search's depth is a property of the data: guarded (_asym_generator_now)."""
+        noise_mode, G, seed = self._noise_cfg()
+        if not all_pairs or every_pair or literal:
+            noise_mode = ops.hash_noise_mode(noise_mode)
+        elif noise_mode == ops.NOISE_RANKED:
+            noise_mode = self._asym_generator_now(x, seed)
+        return noise_mode, G, seed
 
-            u-v-deg       edge_encode.0 [h, 2h+2] on [u, v, deg_u, deg_v]       (dgm.py:1645-1670; raw degrees)
-            u-v-A_uv      edge_encode.0 [h, 2h+1] on [u, v, a_uv]               (dgm.py:1628-1644)
-            u-v-deg-dist  edge_encode.0 [h, 2h+3] on [u, v, deg_u, deg_v, exp(-||u-v||)]   (dgm.py:1671-1702)
-            edge_conv     theta(v-u) + phi(u) = (phi-theta) u + theta v, bias b_theta + b_phi, no activation (1703-1719)
-            A_uv          adj_project(a_uv): hidden width 1, A = B = 0          (dgm.py:1720-1725)"""
-        h, mode = self.latent_dim, self.edge_prob_net_mode
-        d = dict(wdu=None, wdv=None, wex=None, ex_mode=0, t_ex=0.0, act=ops.ACT_LEAKY)
-        ex_in = None
-        if mode in ("u-v-deg", "u-v-A_uv", "u-v-deg-dist"):
-            W0 = self.edge_encode[0].weight
-            need = {"u-v-deg": 2, "u-v-A_uv": 1, "u-v-deg-dist": 3}[mode]
-            assert W0.shape[1] == 2 * h + need, f"edge mode {mode!r} needs extra_edge_dim={need} (edge_encode.0 is {tuple(W0.shape)})"
+    def _scorer(self):
+        """this module's record of _SCORERS; None for u-v-dist"""
+        return _SCORERS.get(self.edge_prob_net_mode)
+
+    def _edge_encode_w0(self, sc):
+        W0, h = self.edge_encode[0].weight, self.latent_dim       # [h, 2h + extras], columns [u | v | extras] (dgm.py:1101-1105)
+        assert W0.shape[1] == 2 * h + sc.extras, f"edge mode {self.edge_prob_net_mode!r} needs extra_edge_dim={sc.extras} (edge_encode.0 is {tuple(W0.shape)})"
+        return W0
+
+    def _edge_mlp_terms(self, avals):
+        """The reference's scorer parameters in the per-node / per-edge form of dgg_edge_mlp_fwd (differentiable slicing) -> (terms, ex_in).
+        The u-v-* scorers: edge_encode.0 [h, 2h + extras] on [u, v, extras] with the extras of _SCORERS (deg_u, deg_v raw; a_uv; exp(-||u-v||))."""
+        h, mode, sc = self.latent_dim, self.edge_prob_net_mode, self._scorer()
+        d = dict(wdu=None, wdv=None, wex=None, ex_mode=sc.ex_mode, t_ex=sc.t_ex, act=sc.act)
+        if sc.extras is not None:
+            W0 = self._edge_encode_w0(sc)
             d.update(Wcat=torch.cat([W0[:, :h], W0[:, h:2 * h]], 0), b1=self.edge_encode[0].bias,
                      w2=self.edge_encode[2].weight.reshape(-1), b2=self.edge_encode[2].bias)
-            if mode != "u-v-A_uv":
-                d.update(wdu=W0[:, 2 * h], wdv=W0[:, 2 * h + 1])
-            if mode == "u-v-A_uv":
-                d.update(wex=W0[:, 2 * h], ex_mode=1)
-                ex_in = avals
-            if mode == "u-v-deg-dist":
-                d.update(wex=W0[:, 2 * h + 2], ex_mode=2, t_ex=-1.0)
-        elif mode == "edge_conv":
+            d.update({k_: W0[:, 2 * h + c_] for k_, c_ in zip(("wdu", "wdv", "wex"), sc.cols) if c_ is not None})
+        elif mode == "edge_conv":                        # theta(v-u) + phi(u) = (phi-theta) u + theta v, bias b_theta + b_phi, no activation
             Th, Ph = self.edge_conv_theta, self.edge_conv_phi
             d.update(Wcat=torch.cat([Ph.weight - Th.weight, Th.weight], 0), b1=Th.bias + Ph.bias,
-                     w2=self.edge_conv_encode.weight.reshape(-1), b2=self.edge_conv_encode.bias, act=ops.ACT_NONE)
-        else:
+                     w2=self.edge_conv_encode.weight.reshape(-1), b2=self.edge_conv_encode.bias)
+        else:                                            # A_uv: adj_project(a_uv), hidden width 1, A = B = 0
             w = self.adj_project.weight
             d.update(Wcat=torch.zeros((2, h), device=w.device, dtype=w.dtype), b1=self.adj_project.bias, w2=torch.ones_like(w).reshape(-1),
-                     b2=torch.zeros_like(self.adj_project.bias), wex=w.reshape(-1), ex_mode=1, act=ops.ACT_NONE)
-            ex_in = avals
-        return d, ex_in
+                     b2=torch.zeros_like(self.adj_project.bias), wex=w.reshape(-1))
+        return d, (avals if sc.reads_adj else None)
 
     def _project_for_k(self, x, literal=False):
         """k-net modes x / gcn-x-deg: leaky(x Wk + bk), together with the scorer's projection where one pass over x serves both
@@ -1258,26 +1243,146 @@ class DGG_LearnableK_debug(nn.Module):
             raise NotImplementedError("all-pairs candidates: the raw probability matrix is dense [N,N]")
         if isinstance(in_adj, (EllAdjacency, CsrAdjacency)):
             in_adj = in_adj.to_sparse().detach()
-        in_adj = in_adj.coalesce()
-        pattern = csr_pattern(in_adj)
-        _, _, deg = csr_candidates(in_adj)
-        We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
-        cfg = dict(cand=pattern, t=ops.T_DIST)
-        if self.edge_prob_net_mode == "u-v-dist":
-            p = _DGGScoresFn.apply(x, None, None, We, be, None, None, None, None, None, None, None, cfg)
-        else:
-            mlp, ex_in = self._edge_mlp_terms(in_adj.values().to(torch.float32))
-            cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
-            p = _DGGScoresFn.apply(x, deg, ex_in, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"], mlp["w2"],
-                                   mlp["b2"], cfg)
+        p, pattern = self._edge_probs(x, in_adj)
         if self.args.perturb_edge_prob and self.args.debug_step != 0:
             noise_mode, G, seed = self._noise_cfg()
             p = ops.CsrPerturbFn.apply(p, pattern[0], pattern[1], pattern[2], x.shape[0], noise_mode, G, seed)
         return CsrAdjacency(pattern[0], pattern[1], pattern[2], p, x.shape[0])
 
+    def _edge_probs(self, x, in_adj, pattern=None, deg=None, rows=None):
+        """raw edge probabilities of the stored entries of in_adj -- or of `pattern` with the degrees `deg` (the complete pattern of all-pairs
+        candidates, u-v-dist), or of the rows (r0, r1) of a row shard -- in CSR order (_DGGScoresFn) -> (p, the pattern they are on)"""
+        We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
+        if pattern is None:
+            in_adj = in_adj.coalesce()
+            pattern, deg = csr_pattern(in_adj), csr_candidates(in_adj)[2]
+        if rows is not None:
+            pattern, (e0, e1) = csr_pattern_rows(in_adj, rows)
+        cfg = dict(cand=pattern, t=ops.T_DIST, rows=rows)
+        if self._scorer() is None:
+            return _DGGScoresFn.apply(x, None, None, We, be, *(None,) * 7, cfg), pattern
+        avals = in_adj.values().to(torch.float32)
+        mlp, ex_in = self._edge_mlp_terms(avals if rows is None else avals[e0:e1])
+        cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
+        return _DGGScoresFn.apply(x, deg, ex_in, We, be, *_sc_terms(mlp), cfg), pattern
+
     def _scorer_prior(self, prior):
         """the prior's CSR arrays for a scorer that reads them (u-v-A_uv), else None: the other scorers ignore a prior"""
-        return prior[:3] if (prior is not None and self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS_PRIOR) else None
+        return prior[:3] if (prior is not None and getattr(self._scorer(), "allpairs", None) == "prior") else None
+
+    def _check_modes(self):
+        """stage 1 of forward: the three mode arguments ("pass" returns k = None, which the reference's own select_top_k cannot consume,
+        dgm.py:1485, 1412)"""
+        if self.edge_prob_net_mode != "u-v-dist" and self._scorer() is None:
+            raise Exception("mode not found")
+        if self.k_net_mode not in ("x", "gcn-x-deg", "input_deg", "learn_normalized_degree"):
+            raise NotImplementedError(f"k-net mode {self.k_net_mode!r}: the HIP path implements 'x', 'gcn-x-deg', 'input_deg' "
+                                      "and 'learn_normalized_degree'")
+        if self.k_select_mode not in ("k_times_edge_prob", "k_only", "edge_p-cdf"):
+            raise Exception("mode not found")
+
+    def _allpairs_mlp_ok(self, prior):
+        """this edge-MLP scorer on all-pairs candidates (that carry `prior`, or None) -> (it is defined there, its latent and hidden width
+        are among those dgg_allpairs_mlp_topk is built for -- edge_conv's hidden width is latent_dim / 2)"""
+        sc, h = self._scorer(), self.latent_dim
+        return (sc.allpairs == "yes" or (sc.allpairs == "prior" and prior is not None),
+                h in ops.KERNEL_WIDTHS and sc.hidden(h) in ops.KERNEL_WIDTHS)
+
+    def _check_all_pairs(self, prior):
+        """stage 1 of forward, all-pairs candidates: what they are not defined for (_fused_outside reports _allpairs_mlp_ok as two clauses)"""
+        mode = self.edge_prob_net_mode
+        runs, widths_ok = self._allpairs_mlp_ok(prior) if mode != "u-v-dist" else (True, True)
+        if mode == "A_uv" and prior is not None:
+            raise NotImplementedError("all-pairs candidates with a prior: the scorer 'A_uv' (hidden width 1, outside the kernel's widths) is a function "
+                                      "of the prior entry only, so every non-edge of a row ties and the selection degenerates to 'prior edges, then "
+                                      "lowest columns'; use 'u-v-A_uv' (or edge-list candidates)")
+        if not runs:
+            raise NotImplementedError(f"all-pairs candidates are defined for 'u-v-dist' and the edge-MLP scorers {_EDGE_MLP_ALLPAIRS} "
+                                      f"only: {mode!r} reads the stored values of in_adj (dgm.py:1628-1644, "
+                                      "1720-1725), which all-pairs candidates do not have")
+        if not widths_ok or (mode != "u-v-dist" and self.ell_width > 64):
+            raise NotImplementedError(f"edge-MLP scorers {_EDGE_MLP_ALLPAIRS} on all-pairs candidates: latent_dim in (16, 32, 64, 128) "
+                                      "(edge_conv: from 32), ell_width <= 64")
+        if self.k_net_mode == "gcn-x-deg" and prior is None:
+            raise NotImplementedError("k-net mode 'gcn-x-deg' aggregates over the stored entries of in_adj, which all-pairs candidates "
+                                      "do not have (k-net modes 'x', 'input_deg', 'learn_normalized_degree' run on them; "
+                                      "AllPairs(prior_degree, prior=graph) carries the entries)")
+
+    @staticmethod
+    def _candidates(in_adj, per_edge=False):
+        """stage 2 of forward and _forward_conv -> (in_adj as used from here on, cand, deg, prior, erow, avals).  AllPairs: cand None, deg its
+        prior degrees, prior = prior_csr() (or None).  Edge list (an EllAdjacency -- dgg_adj_input != "input_adj": the previous learned graph --
+        is converted): cand = (rowptr, col), deg the row sums; per_edge: the entries' rows and stored values as the edge-MLP scorers read them."""
+        if isinstance(in_adj, AllPairs):
+            return in_adj, None, in_adj.prior_degree, in_adj.prior_csr(), None, None
+        if isinstance(in_adj, EllAdjacency):
+            in_adj = in_adj.to_sparse().detach()
+        rowptr, col, deg = csr_candidates(in_adj)
+        erow = avals = None
+        if per_edge:
+            in_adj = in_adj.coalesce()
+            erow, avals = in_adj.indices()[0].to(torch.int32), in_adj.values().to(torch.float32)
+        return in_adj, (rowptr, col), deg, None, erow, avals
+
+    def _learned_k(self, x, in_adj, cand, deg, prior, literal):
+        """stage 3 of forward: the k-net of args.dgg_mode_k_net -> (xp or None: the scorer's projection where one pass over x served both, k [N])"""
+        kn, xp_dual = self.k_net, None
+        consts = (float(self.deg_mean), float(self.deg_std)) if self.k_net_mode == "input_deg" else None
+        stochastic = getattr(self.args, "stochastic_k", False) and self.training
+        if self.k_net_mode in ("x", "gcn-x-deg"):
+            xp_dual, xk = self._project_for_k(x, literal)
+            if self.k_net_mode == "gcn-x-deg":       # relu(normalize_adj(in_adj) @ xk @ k_W)   (dgm.py:1528-1540)
+                # (all-pairs candidates that carry a prior: normalize_adj(prior) @ xk on the prior's pattern)
+                pat = (prior[0], prior[1], prior[3], prior[2]) if cand is None else (*csr_pattern(in_adj), in_adj.coalesce().values().float())
+                xk = ops.LinearFn.apply(CsrAdjacency(*pat, x.shape[0]).normalize().matmul(xk), self.k_W, None, ops.ACT_RELU, 1)
+            k = (self._stochastic_k(torch.cat([xk, self._norm_deg(deg, None, 1e-5)[0].unsqueeze(1)], 1), deg, None, embed=True)
+                 if stochastic else self._knet_feat(xk, deg))
+        elif stochastic:
+            nd, _, _ = self._norm_deg(deg, consts, 1e-5 if consts is not None else 0.0)
+            in3 = nd.unsqueeze(1) * self.input_degree_project.weight.reshape(1, -1) + self.input_degree_project.bias
+            k = self._stochastic_k(in3, deg, consts, embed=False)
+        else:
+            k = _KnetDegFn.apply(deg, self.input_degree_project.weight, self.input_degree_project.bias, kn.k_mu.weight,
+                                 kn.k_mu.bias, kn.k_project.weight, kn.k_project.bias, consts)
+        return xp_dual, k
+
+    def _scorer_node(self, x, k, cfg, xp_dual, deg, prior, erow, avals):
+        """stage 5 of forward: the node of this scorer, candidate form (cfg["cand"]) and row form (cfg["layout"]: chunked rows) -> w, idx, val, rs"""
+        We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
+        if self._scorer() is None:                   # u-v-dist
+            if "layout" in cfg:                      # (the ranked symmetric generator has no wide-row form: its per-pair hash, ops.allpairs_topk_wide)
+                cfg["wide_noise"] = {ops.NOISE_RANKED_SYM: ops.NOISE_HASH_SYM}.get(cfg["noise_mode"], cfg["noise_mode"])
+                xp_dual = xp_dual if xp_dual is not None else ops.LinearFn.apply(x, We, be, ops.ACT_LEAKY, 0)
+            if xp_dual is not None:
+                cfg["want_bwd"] = ops.backward_will_follow(xp_dual, k)
+                return (_DGGWideAdjFn if "layout" in cfg else _DGGSoftAdjXpFn).apply(xp_dual, k, cfg)
+            cfg["want_bwd"] = ops.backward_will_follow(x, k, We, be)
+            return _DGGSoftAdjFn.apply(x, k, We, be, cfg)
+        mlp, ex_in = self._edge_mlp_terms(avals)
+        cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
+        if cfg["cand"] is None:                      # all-pairs candidates: the prior degrees are the degrees; u-v-A_uv: the extra of a pair
+            cfg["prior"] = self._scorer_prior(prior)     # is the prior's stored value, looked up inside the sweep
+            return (_DGGAllPairsMlpWideAdjFn if "layout" in cfg else _DGGAllPairsMlpAdjFn).apply(x, k, deg, We, be, *_sc_terms(mlp), cfg)
+        cfg["cand"] = cfg["cand"] + (erow,)
+        return _DGGEdgeMlpAdjFn.apply(x, k, deg, ex_in, We, be, *_sc_terms(mlp), cfg)
+
+    def _list_result(self, x, k, cfg, out, cand, chunk_checked, literal, writer, epoch):
+        """stage 6 of forward, rows on the 64-rank list: overflow tracking, generator status, the writer's scalars, literal dgg_hard"""
+        w, idx, val, rs = out
+        k = k.detach()
+        if not chunk_checked:                    # (chunk_checked: the layout just read back says every row fits the list)
+            self._track_overflow(k, None if cand is None else (cand[0][1:] - cand[0][:-1]))
+        if cfg.get("rsym_fell_back"):
+            self._sym_switch()
+        self._note_rsym(cfg, x.shape[0])
+        self._log_first_k(writer, epoch, cfg, w, val)
+        if literal:
+            # reference dgm.py:1294-1311 to the letter: ones where the RANK of a column equals the column INDEX of a strong neighbour
+            We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
+            xp = ops.linear_fwd(x.detach(), We.detach(), be.detach(), ops.ACT_LEAKY)
+            hval, hidx = ops.LiteralHardFn.apply(w, idx, xp, cand, cfg["t"], cfg["noise_mode"], cfg["G"], cfg["seed"])
+            return EllAdjacency(hidx, hval, x.shape[0], owner=self)
+        return EllAdjacency(idx, w, x.shape[0], rs=rs, k=k, score=val, part=cfg.get("part"), owner=self)
 
     def forward(self, x, in_adj, noise=True, writer=None, epoch=None):
         """x [N,dim] fp32 on the GPU; in_adj: sparse COO [N,N] (coalesced, self loops added by the caller) whose
@@ -1285,62 +1390,25 @@ class DGG_LearnableK_debug(nn.Module):
         exactly like the reference (perturbation is gated by args.perturb_edge_prob only, dgm.py:1211).
         `AllPairs(prior_degree, prior=P)`: every pair is a candidate and the input graph P is seen -- the scorer u-v-A_uv reads P's
         stored value of a pair (0 for a non-edge) and the k-net gcn-x-deg aggregates over P; the reference equivalent is the complete
-        in_adj that stores P's values.  P is used as given (no self loops are added)."""
+        in_adj that stores P's values.  P is used as given (no self loops are added).
+        The stages: modes and refusals -> candidates -> noise (_noise_now) -> learned degree -> row form (the CSR form, chunked rows or
+        the 64-rank list) -> the scorer's node -> bookkeeping.  Which node and kernel a configuration ends in, under which argument,
+        and what is refused: the route table of DESIGN.md section 5."""
         assert x.ndim == 2 and len(in_adj.shape) == 2
-        if self.edge_prob_net_mode != "u-v-dist" and self.edge_prob_net_mode not in _EDGE_MLP_MODES:
-            raise Exception("mode not found")
-        if self.k_net_mode not in ("x", "gcn-x-deg", "input_deg", "learn_normalized_degree"):
-            # "pass" returns k = None, which the reference's own select_top_k cannot consume (dgm.py:1485, 1412)
-            raise NotImplementedError(f"k-net mode {self.k_net_mode!r}: the HIP path implements 'x', 'gcn-x-deg', 'input_deg' "
-                                      "and 'learn_normalized_degree'")
-        if self.k_select_mode not in ("k_times_edge_prob", "k_only", "edge_p-cdf"):
-            raise Exception("mode not found")
+        self._check_modes()
         if self.args.debug_step in (0, 1) or self.k_select_mode == "edge_p-cdf":
             return self._scores_adjacency(x, in_adj)
-        avals = erow = None
-        prior = in_adj.prior_csr() if isinstance(in_adj, AllPairs) else None
-        if isinstance(in_adj, AllPairs):
-            if self.edge_prob_net_mode == "A_uv" and prior is not None:
-                raise NotImplementedError("all-pairs candidates with a prior: the scorer 'A_uv' (hidden width 1, outside the kernel's widths) is "
-                                          "a function of the prior entry only, so every non-edge of a row ties and the selection degenerates "
-                                          "to 'prior edges, then lowest columns'; use 'u-v-A_uv' (or edge-list candidates)")
-            if self.edge_prob_net_mode != "u-v-dist" and self.edge_prob_net_mode not in _EDGE_MLP_ALLPAIRS and not (
-                    prior is not None and self.edge_prob_net_mode in _EDGE_MLP_ALLPAIRS_PRIOR):
-                raise NotImplementedError(f"all-pairs candidates are defined for 'u-v-dist' and the edge-MLP scorers {_EDGE_MLP_ALLPAIRS} "
-                                          f"only: {self.edge_prob_net_mode!r} reads the stored values of in_adj (dgm.py:1628-1644, "
-                                          "1720-1725), which all-pairs candidates do not have")
-            if self.edge_prob_net_mode != "u-v-dist" and (
-                    self.latent_dim not in (16, 32, 64, 128) or (self.edge_prob_net_mode == "edge_conv" and self.latent_dim == 16) or self.ell_width > 64):
-                # (the widths dgg_allpairs_mlp_topk is built for; edge_conv's hidden width is latent_dim / 2)
-                raise NotImplementedError(f"edge-MLP scorers {_EDGE_MLP_ALLPAIRS} on all-pairs candidates: latent_dim in (16, 32, 64, 128) "
-                                          "(edge_conv: from 32), ell_width <= 64")
-            if self.k_net_mode == "gcn-x-deg" and prior is None:
-                raise NotImplementedError("k-net mode 'gcn-x-deg' aggregates over the stored entries of in_adj, which all-pairs candidates "
-                                          "do not have (k-net modes 'x', 'input_deg', 'learn_normalized_degree' run on them; "
-                                          "AllPairs(prior_degree, prior=graph) carries the entries)")
-            cand, deg = None, in_adj.prior_degree
-        else:
-            if isinstance(in_adj, EllAdjacency):     # dgg_adj_input != "input_adj": previous learned graph
-                in_adj = in_adj.to_sparse().detach()
-            rowptr, col, deg = csr_candidates(in_adj)
-            cand = (rowptr, col)
-            if self.edge_prob_net_mode != "u-v-dist":
-                in_adj = in_adj.coalesce()
-                erow, avals = in_adj.indices()[0].to(torch.int32), in_adj.values().to(torch.float32)
-        noise_mode, G, seed = self._noise_cfg()
+        mlp, N = self._scorer() is not None, x.shape[0]
+        in_adj, cand, deg, prior, erow, avals = self._candidates(in_adj, per_edge=mlp)
+        if cand is None:
+            self._check_all_pairs(prior)
         literal = bool(self.hard and getattr(self.args, "dgg_hard_literal", False))
-        ap_mlp = cand is None and self.edge_prob_net_mode != "u-v-dist"     # edge-MLP scorer on all-pairs candidates: every pair is scored
-        if noise_mode == ops.NOISE_RANKED and cand is None and not literal and not ap_mlp:
-            noise_mode = self._asym_generator_now(x, seed)       # the ranked search's depth is a property of the data: guarded
-        if noise_mode == ops.NOISE_RANKED_SYM and (cand is not None or literal or ap_mlp):
-            noise_mode = ops.NOISE_HASH_SYM
-        if noise_mode == ops.NOISE_RANKED and (cand is not None or literal or ap_mlp):
-            noise_mode = ops.NOISE_HASH              # edge-list candidates: every candidate is scored, per-pair hash noise
-                                                     # (literal dgg_hard: the full ranking of a row needs per-pair noise as well)
+        ap_mlp = cand is None and mlp                # edge-MLP scorer on all-pairs candidates: every pair is scored
+        noise_mode, G, seed = self._noise_now(x, cand is None, ap_mlp, literal)
         cfg = dict(cand=cand, K=self.ell_width, t=ops.T_DIST, noise_mode=noise_mode, G=G, seed=seed, algo=self.topk_algo,
                    sym_fallback=getattr(self.args, "dgg_sym_generator", "auto") != "ranked",
                    mode=ops.MODE_K_TIMES_EDGE_PROB if self.k_select_mode == "k_times_edge_prob" else ops.MODE_K_ONLY)
-        if literal and (self.edge_prob_net_mode != "u-v-dist" or x.shape[0] > 8192):
+        if literal and (mlp or N > 8192):
             raise NotImplementedError("dgg_hard_literal: the literal return_hard_or_soft needs the full ranking of every row's N scores "
                                       "(u-v-dist scorer, N <= 8192); use the default straight-through dgg_hard otherwise (edge lists, "
                                       f"and all-pairs candidates under 'u-v-dist' or {_EDGE_MLP_ALLPAIRS})")
@@ -1350,97 +1418,27 @@ class DGG_LearnableK_debug(nn.Module):
             # return_hard_or_soft (dgm.py:1294-1311) scatters an already-unsorted matrix through the sort permutation, which is
             # not a function of the graph; args.dgg_hard_literal=True reproduces it (small graphs).
             cfg["fwd_mode"] = ops.MODE_HARD_ST
-        We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
-        kn = self.k_net
-        xp_dual = None
-        if self.k_net_mode in ("x", "gcn-x-deg"):
-            xp_dual, xk = self._project_for_k(x, literal)
-            if self.k_net_mode == "gcn-x-deg":       # relu(normalize_adj(in_adj) @ xk @ k_W)   (dgm.py:1528-1540)
-                if cand is None:                 # all-pairs candidates that carry a prior: normalize_adj(prior) @ xk on the prior's pattern
-                    nadj = CsrAdjacency(prior[0], prior[1], prior[3], prior[2], x.shape[0]).normalize()
-                else:
-                    pat = csr_pattern(in_adj)
-                    nadj = CsrAdjacency(pat[0], pat[1], pat[2], in_adj.coalesce().values().float(), x.shape[0]).normalize()
-                xk = ops.LinearFn.apply(nadj.matmul(xk), self.k_W, None, ops.ACT_RELU, 1)
-            if getattr(self.args, "stochastic_k", False) and self.training:
-                k = self._stochastic_k(torch.cat([xk, self._norm_deg(deg, None, 1e-5)[0].unsqueeze(1)], 1), deg, None, embed=True)
-            else:
-                k = self._knet_feat(xk, deg)
-        elif getattr(self.args, "stochastic_k", False) and self.training:
-            consts = (float(self.deg_mean), float(self.deg_std)) if self.k_net_mode == "input_deg" else None
-            nd, _, _ = self._norm_deg(deg, consts, 1e-5 if consts is not None else 0.0)
-            in3 = nd.unsqueeze(1) * self.input_degree_project.weight.reshape(1, -1) + self.input_degree_project.bias
-            k = self._stochastic_k(in3, deg, consts, embed=False)
-        else:
-            consts = (float(self.deg_mean), float(self.deg_std)) if self.k_net_mode == "input_deg" else None
-            k = _KnetDegFn.apply(deg, self.input_degree_project.weight, self.input_degree_project.bias, kn.k_mu.weight,
-                                 kn.k_mu.bias, kn.k_project.weight, kn.k_project.bias, consts)
-        if cand is not None and not literal and self._wide_rows(in_adj, rowptr, k):
-            # rows wider than the ELL and learned degrees that may exceed it: the CSR form (no width limit)
+        xp_dual, k = self._learned_k(x, in_adj, cand, deg, prior, literal)
+        if cand is not None and not literal and self._wide_rows(in_adj, cand[0], k):
+            # row form: rows wider than the ELL and learned degrees that may exceed it take the CSR form (no width limit)
             return self._csr_soft_adjacency(x, in_adj, k, noise_mode, G, seed, cfg["mode"])
-        if cand is None and not literal and self._chunk_policy(noise_mode) and not _capturing():
-            # learned degrees beyond the 64-rank list: chunked rows (same generator, same search, ceil(k_i + 8.5) + 1 ranks per row)
-            lay = ops.chunk_layout(k.detach(), ncols=x.shape[0])          # (one readback: the chunk count sizes the arrays)
+        chunk_checked = False
+        if cand is None and not literal and (self._allpairs_mlp_chunked() if ap_mlp else self._chunk_policy(noise_mode)) and not _capturing():
+            # learned degrees beyond the 64-rank list: chunked rows, ceil(k_i + 8.5) + 1 ranks per row in chunks of 64 (same generator, same search)
+            lay = ops.chunk_layout(k.detach(), ncols=N)                   # (one readback: the chunk count sizes the arrays)
             if lay is not None and lay.wide:
                 cfg["layout"] = lay
-                cfg["wide_noise"] = {ops.NOISE_RANKED_SYM: ops.NOISE_HASH_SYM}.get(noise_mode, noise_mode)
-                xp = xp_dual if xp_dual is not None else ops.LinearFn.apply(x, We, be, ops.ACT_LEAKY, 0)
-                cfg["want_bwd"] = ops.backward_will_follow(xp, k)
-                w, idx, val, rs = _DGGWideAdjFn.apply(xp, k, cfg)
-                self._log_first_k_chunked(writer, epoch, cfg, w, val, lay)
-                return EllAdjacency(idx, w, x.shape[0], rs=rs, k=k.detach(), score=val, owner=self, layout=lay)
+                w, idx, val, rs = self._scorer_node(x, k, cfg, xp_dual, deg, prior, erow, avals)
+                self._log_first_k(writer, epoch, cfg, w, val, lay)
+                return EllAdjacency(idx, w, N, rs=rs, k=k.detach(), score=val, owner=self, layout=lay)
             chunk_checked = lay is not None
-        elif ap_mlp and self._allpairs_mlp_chunked() and not _capturing():
-            # the same for the edge-MLP scorers (args.dgg_allpairs_mlp_rows = "chunked"): every pair is scored, a row keeps its
-            # ceil(k_i + 8.5) + 1 best in chunks of 64 (dgg_allpairs_mlp_topk_wide)
-            lay = ops.chunk_layout(k.detach(), ncols=x.shape[0])          # (one readback: the chunk count sizes the arrays)
-            if lay is not None and lay.wide:
-                mlp, _ = self._edge_mlp_terms(None)
-                cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], layout=lay, prior=self._scorer_prior(prior))
-                w, idx, val, rs = _DGGAllPairsMlpWideAdjFn.apply(x, k, deg, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"],
-                                                                 mlp["w2"], mlp["b2"], cfg)
-                self._log_first_k_chunked(writer, epoch, cfg, w, val, lay)
-                return EllAdjacency(idx, w, x.shape[0], rs=rs, k=k.detach(), score=val, owner=self, layout=lay)
-            chunk_checked = lay is not None
-        else:
-            chunk_checked = False
-        if cand is None and not literal and self.edge_prob_net_mode == "u-v-dist" and not chunk_checked and self._allpairs_wide(x.shape[0], k):
+        if cand is None and not literal and not mlp and not chunk_checked and self._allpairs_wide(N, k):
             # learned degrees beyond the list on all-pairs candidates: every column ranked, CSR form (per-pair hash noise: the ranked
             # generators produce a row's noise in decreasing order for a search that stops early -- here nothing stops early)
-            nm = {ops.NOISE_RANKED: ops.NOISE_HASH, ops.NOISE_RANKED_SYM: ops.NOISE_HASH_SYM}.get(noise_mode, noise_mode)
-            return self._csr_soft_adjacency(x, None, k, nm, G, seed, cfg["mode"], pattern=self._allpairs_pattern(x.shape[0], x.device), deg=deg)
-        if self.edge_prob_net_mode == "u-v-dist" and xp_dual is not None:
-            cfg["want_bwd"] = ops.backward_will_follow(xp_dual, k)
-            w, idx, val, rs = _DGGSoftAdjXpFn.apply(xp_dual, k, cfg)
-        elif self.edge_prob_net_mode == "u-v-dist":
-            cfg["want_bwd"] = ops.backward_will_follow(x, k, We, be)
-            w, idx, val, rs = _DGGSoftAdjFn.apply(x, k, We, be, cfg)
-        elif cand is None:                       # u-v-deg / u-v-deg-dist / edge_conv on all-pairs candidates: the prior degrees are the degrees
-            mlp, _ = self._edge_mlp_terms(None)  # (u-v-A_uv: the extra of a pair is the prior's stored value, looked up inside the sweep)
-            cfg.update(ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"], prior=self._scorer_prior(prior))
-            w, idx, val, rs = _DGGAllPairsMlpAdjFn.apply(x, k, deg, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"], mlp["b1"],
-                                                         mlp["w2"], mlp["b2"], cfg)
-        else:
-            mlp, ex_in = self._edge_mlp_terms(avals)
-            cfg.update(cand=(rowptr, col, erow), ex_mode=mlp["ex_mode"], t_ex=mlp["t_ex"], act=mlp["act"])
-            w, idx, val, rs = _DGGEdgeMlpAdjFn.apply(x, k, deg, ex_in, We, be, mlp["Wcat"], mlp["wdu"], mlp["wdv"], mlp["wex"],
-                                                     mlp["b1"], mlp["w2"], mlp["b2"], cfg)
-        k = k.detach()
-        if not chunk_checked:                    # (chunk_checked: the layout just read back says every row fits the list)
-            self._track_overflow(k, None if cand is None else (rowptr[1:] - rowptr[:-1]))
-        if cfg.get("rsym_fell_back"):
-            self._sym_switch()
-        self._note_rsym(cfg, x.shape[0])
-        if writer is not None:   # the two scalars the reference logs from inside the DGG (dgm.py:1259-1261)
-            f = w.detach() if (cfg["mode"] == ops.MODE_K_ONLY or "fwd_mode" in cfg) else (w.detach() / val.clamp(min=1e-30))
-            writer.add_scalar("values/first_k_std", f.sum(-1).std(), epoch)
-            writer.add_scalar("values/first_k_mean", f.sum(-1).mean(), epoch)
-        if literal:
-            # reference dgm.py:1294-1311 to the letter: ones where the RANK of a column equals the column INDEX of a strong neighbour
-            xp = ops.linear_fwd(x.detach(), We.detach(), be.detach(), ops.ACT_LEAKY)
-            hval, hidx = ops.LiteralHardFn.apply(w, idx, xp, cand, cfg["t"], noise_mode, G, seed)
-            return EllAdjacency(hidx, hval, x.shape[0], owner=self)
-        return EllAdjacency(idx, w, x.shape[0], rs=rs, k=k, score=val, part=cfg.get("part"), owner=self)
+            return self._csr_soft_adjacency(x, None, k, ops.hash_noise_mode(noise_mode), G, seed, cfg["mode"],
+                                            pattern=self._allpairs_pattern(N, x.device), deg=deg)
+        out = self._scorer_node(x, k, cfg, xp_dual, deg, prior, erow, avals)
+        return self._list_result(x, k, cfg, out, cand, chunk_checked, literal, writer, epoch)
 
 
 class _DGGClassFn(torch.autograd.Function):

@@ -203,8 +203,7 @@ class _CsrForm(nn.Module):
         m = self.model
         dgg = m.dggs[0]
         _, _, deg = csr_candidates(in_adj)
-        noise_mode, _, seed = dgg._noise_cfg()               # (edge-list candidates: every candidate is scored, per-pair hash noise)
-        noise_mode = {ops.NOISE_RANKED: ops.NOISE_HASH, ops.NOISE_RANKED_SYM: ops.NOISE_HASH_SYM}.get(noise_mode, noise_mode)
+        noise_mode, _, seed = dgg._noise_now(x, all_pairs=False)    # (edge-list candidates: every candidate is scored, per-pair hash noise)
         mode = ops.MODE_K_TIMES_EDGE_PROB if dgg.k_select_mode == "k_times_edge_prob" else ops.MODE_K_ONLY
         # replicated: the k-net on the whole graph (its degree normalisation reads all N prior degrees); the shard keeps its rows' k
         k = dgg._knet_feat(dgg._project_for_k(x)[1], deg)

@@ -14,6 +14,7 @@ from . import _lib
 
 NOISE_NONE, NOISE_EXPLICIT, NOISE_HASH, NOISE_HASH_SYM, NOISE_RANKED, NOISE_RANKED_SYM = 0, 1, 2, 3, 4, 5
 RSYM_WIDTHS = (8, 16, 32, 64, 128)     # latent widths of the ranked symmetric generator's kernels
+KERNEL_WIDTHS = (16, 32, 64, 128)      # feature widths the width-templated kernels (searches, partitioned backwards, edge-MLP sweeps) are built for
 ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 MODE_K_TIMES_EDGE_PROB, MODE_K_ONLY = 0, 1
 MODE_HARD_ST = 3          # softk_fwd only: value (ramp - score*ramp) + score*ramp, gradient of MODE_K_TIMES_EDGE_PROB
@@ -571,7 +572,7 @@ def edgelist_topk_softk(xp, rowptr, col, k, mode=MODE_K_TIMES_EDGE_PROB, K=DEFAU
     graph's (keyed on global ids).  rows=None: the whole graph, exactly the call without it."""
     xp = _chk(xp)
     N, h = xp.shape
-    if h not in (16, 32, 64, 128):
+    if h not in KERNEL_WIDTHS:
         return None
     rowptr, col, k = _chk(rowptr, torch.int64), _chk(col, torch.int32), _chk(k)
     r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
@@ -1121,7 +1122,7 @@ def csr_uvdist_bwd(xp, rowptr, col, p, dp, t=T_DIST, rows=None):
     return dxp
 
 
-def _hash_noise_mode(noise_mode):
+def hash_noise_mode(noise_mode):
     """the ranked generators serve all-pairs rows only: stored entries take the per-pair hash of the same law"""
     return {NOISE_RANKED: NOISE_HASH, NOISE_RANKED_SYM: NOISE_HASH_SYM}.get(noise_mode, noise_mode)
 
@@ -1132,7 +1133,7 @@ def csr_perturb_fwd(p, erow, col, N, noise_mode, G=None, seed=(0, 0)):
     p = _chk(p)
     erow, col = _chk(erow, torch.int32), _chk(col, torch.int32)
     assert erow.shape == col.shape == p.shape, "csr_perturb_fwd: p, erow, col [E]"
-    noise_mode = _hash_noise_mode(noise_mode)
+    noise_mode = hash_noise_mode(noise_mode)
     ldG = 0
     if noise_mode == NOISE_EXPLICIT:
         G = _chk(G)
@@ -1293,7 +1294,7 @@ def act_bwd(y, dy, act):
     return dp
 
 
-CONV_BWD_WIDTHS = (16, 32, 64, 128)
+CONV_BWD_WIDTHS = KERNEL_WIDTHS
 
 
 def conv_bwd_cols(idx, ahat, H, G, part, rs=None, want_da=False):
@@ -1496,7 +1497,7 @@ def softk_edge_bwd_p(xp, idx, val, k, dA, dA_rec, rs, da, row0, t, perturb, mode
     xp = _chk(xp)
     Ng, h = xp.shape
     N, K = idx.shape
-    if partp is None or h not in (16, 32, 64, 128) or mode not in (MODE_K_TIMES_EDGE_PROB, MODE_K_ONLY) or Ng != partp.ncols:
+    if partp is None or h not in KERNEL_WIDTHS or mode not in (MODE_K_TIMES_EDGE_PROB, MODE_K_ONLY) or Ng != partp.ncols:
         return None
     lay = partp.layout
     nrows = N if lay is None else lay.rows
@@ -1564,7 +1565,7 @@ def softk_edge_bwd(xp, idx, val, k, dA, rs=None, da=None, row0=0, t=T_DIST, pert
     xp = _chk(xp)
     Ng, h = xp.shape
     N, K = idx.shape
-    if part is None or h not in (16, 32, 64, 128) or mode not in (MODE_K_TIMES_EDGE_PROB, MODE_K_ONLY):
+    if part is None or h not in KERNEL_WIDTHS or mode not in (MODE_K_TIMES_EDGE_PROB, MODE_K_ONLY):
         return None
     dxp = _zeros(tuple(xp.shape), xp.device)
     coef = torch.empty(N * K + Ng, device=xp.device, dtype=torch.float32)
@@ -1602,7 +1603,7 @@ def edge_bwd(xp, idx, val, dval, row0=0, t=T_DIST, perturb=False, part=None):
     Ng, h = xp.shape
     N, K = idx.shape
     dxp = _zeros(tuple(xp.shape), xp.device)
-    if part is not None and h in (16, 32, 64, 128):
+    if part is not None and h in KERNEL_WIDTHS:
         coef = torch.empty(N * K + Ng, device=xp.device, dtype=torch.float32)   # per-record coefficients + column sums
         val, dval = _chk(val), _chk(dval)
         pe = _probe_begin()

@@ -45,6 +45,8 @@ import weakref
 import torch
 import torch.distributed as dist
 
+from .ops import KERNEL_WIDTHS, RSYM_WIDTHS        # (constants only: the kernels themselves come in through `kern`)
+
 
 def shard_bounds(N, world, rank):
     per = (N + world - 1) // world
@@ -391,7 +393,7 @@ class ShardedDGGConv:
         at N = 100 000) the same stop test uses G + log p_max(i).  tight_bound: "off" | "on" | "auto" = on when a pilot walk (~1000
         sampled rows, 64-block budget, every 16th forward and never inside a capture) puts the search's cost above 2.5 x the sweep's."""
         kern = self.kern
-        if self.tight_bound == "off" or xp.shape[1] not in (16, 32, 64, 128) or self.t >= 0:
+        if self.tight_bound == "off" or xp.shape[1] not in KERNEL_WIDTHS or self.t >= 0:
             return None
         if self.tight_bound == "auto":
             capturing = xp.is_cuda and torch.cuda.is_current_stream_capturing()
@@ -525,9 +527,9 @@ class ShardedDGGConv:
             return self._search_edge_list(s, deg_full)
         if self.scorer is not None:
             return self._search_allpairs_mlp(s, deg_full)
-        if self.noise_mode == 4 and self.K == 64 and xp.shape[1] in (8, 16, 32, 64, 128):
+        if self.noise_mode == 4 and self.K == 64 and xp.shape[1] in RSYM_WIDTHS:
             # ranked noise: the ramp is applied inside the search kernel, while the settled list is still in registers
-            s["layout"] = lay = self._chunk_layout(k) if xp.shape[1] in (16, 32, 64, 128) else None
+            s["layout"] = lay = self._chunk_layout(k) if xp.shape[1] in KERNEL_WIDTHS else None
             lkw_ = {}
             lp = self._row_bound(xp, k)             # upper bounds of log p over a row's other nodes, when the walk is deep enough to pay for them
             if lp is not None:
@@ -541,7 +543,7 @@ class ShardedDGGConv:
         # the generators without a row-wise early-stopping search (unperturbed scores, per-pair hash noise, the ranked symmetric
         # generator).  Rows wider than 64 ranks: chunked rows through the threshold-buffer evaluator (any width; the reference's
         # defaults symmetric_noise=True / perturb_edge_prob=False train into this regime like every other configuration)
-        s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)) else None
+        s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in KERNEL_WIDTHS and self.mode in (0, 1)) else None
         if lay is not None:
             return kern.allpairs_topk_wide(xp, k, lay, self.mode, self.t, self.seed, rows=(self.r0, self.r1),
                                            noise_mode=self.WIDE_NOISE[self.noise_mode])
@@ -605,7 +607,7 @@ class ShardedDGGConv:
         # u-v-A_uv against a prior graph: the WHOLE graph's CSR arrays on every rank (the kernel looks up the pairs of its row range);
         # handed on only when the scorer carries one -- the contract's entries, and a stand-in written to them, take no prior=
         pk = {} if sc.get("prior") is None else {"prior": sc["prior"]}
-        s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)) else None
+        s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in KERNEL_WIDTHS and self.mode in (0, 1)) else None
         if lay is not None:                         # rows wider than 64 ranks: ceil(k_i + 8.5) + 1 ranks of every row, the ramp fused
             got = kern.allpairs_mlp_topk_wide(*terms, k, lay, self.mode, nm, None, self.seed, rows=rows, **pk)
             if got is None:
@@ -636,7 +638,7 @@ class ShardedDGGConv:
         normalize_adj fused into its fill pass -- when the namespace offers it and covers the shape), else part (index form), ahat,
         partp_sorted (False: want_backward was off and the sort was not launched), side_join (the sort runs on the side stream)."""
         kern, rs, lay = self.kern, s["rs"], s["layout"]
-        use_p = s["xp"].shape[1] in (16, 32, 64, 128) and s["H_loc"].shape[1] in (16, 32, 64, 128) and self.mode in (0, 1)
+        use_p = s["xp"].shape[1] in KERNEL_WIDTHS and s["H_loc"].shape[1] in KERNEL_WIDTHS and self.mode in (0, 1)
         ov = use_p and self.overlap and self.overlap_sort and s["idx"].is_cuda
         # want_backward = False (set by the autograd node under torch.no_grad() / frozen parameters): the per-bucket sort of the
         # partition -- read by the backward's column kernels only -- is not launched at all (ADVICE round 4: an eval forward used to
@@ -769,7 +771,7 @@ class ShardedDGGConv:
             assert pc is not None
             return pc + (s["ahat"],)
         cols = None
-        if self.scorer is None and dA_ext is None and part is not None and s["xp"].shape[1] in (16, 32, 64, 128) and self.mode in (0, 1):
+        if self.scorer is None and dA_ext is None and part is not None and s["xp"].shape[1] in KERNEL_WIDTHS and self.mode in (0, 1):
             cols = kern.conv_bwd_cols(s["idx"], s["ahat"], s["H"], G, part, s["rs"], True)
         if cols is not None:                        # index partition
             dA, dH, da = cols
