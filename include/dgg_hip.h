@@ -386,8 +386,9 @@ int dgg_edge_mlp_bwd_det(const float *AB, int64_t N, int hw, int64_t row0, int64
 /* the same for an ELL block whose payload partition (dgg_partp_build of (idx, w), with its entry -> record map: dgg_partp_has_map(N))
  * is at hand: the neighbour-side sums d B_j WITHOUT float atomics -- every selected entry's term is stored as a row of dz_rec in
  * record order (the records of a destination node are consecutive) and a second kernel adds each node's rows.  w [N,K]: the weights
- * the partition was built from; dz_rec: dz_rows * hw floats of scratch, dz_rows >= the number of records (the number of candidate
- * edges bounds it); hw a multiple of 4. */
+ * the partition was built from (an entry has a record iff idx >= 0 and w != 0; a selected entry with w == 0 and a non-zero cotangent
+ * has none and goes to dAB by float atomics); dz_rec: dz_rows * hw floats of scratch, dz_rows >= the number of records (the number
+ * of candidate edges bounds it); hw a multiple of 4. */
 int dgg_edge_mlp_bwd_partp(const float *AB, int64_t N, int hw, const int32_t *idx, const int32_t *eid, const float *val, const float *dval,
                            const float *w, int K, const float *deg, const float *ex, const float *wdu, const float *wdv, const float *wex,
                            const float *b1, const float *w2, const float *b2, int act, int perturb, const void *partp_ws, int64_t ncols,

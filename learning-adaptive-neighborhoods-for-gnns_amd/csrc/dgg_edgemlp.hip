@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
         // a non-zero cotangent are visited (a citation graph fills ~6 of the 64 slots: 2 batches of dependent gathers instead of 16)
         const bool ellrow = !rowptr && K <= 64;
         int32_t jrow = -1;
-        float grow = 0.0f;
+        float grow = 0.0f, wlane = 0.0f;                             // (wlane: the weight the partition was built from; recs_on only)
         const bool recs_on = VEC == 4 && dz_rec != nullptr && ellrow_ok(rowptr, K);
         if (ellrow) {
             if (lane < K) { jrow = idx[base + lane]; grow = dval[base + lane]; }
@@ -181,8 +181,8 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
             if (dex && lane < K) dex[base + lane] = 0.0f;           // (the visited batches overwrite their entries below)
             cnt = am ? 64 - __builtin_clzll(am) : 0;
             if (recs_on) {                                           // recorded entries without a cotangent: zero rows (rare)
-                const float wl = lane < K ? wrow[base + lane] : 0.0f;
-                uint64_t zm = __ballot(jrow >= 0 && wl != 0.0f && grow == 0.0f);
+                wlane = lane < K ? wrow[base + lane] : 0.0f;
+                uint64_t zm = __ballot(jrow >= 0 && wlane != 0.0f && grow == 0.0f);
                 while (zm != 0ull) {                                 // wave-uniform
                     const int r = __builtin_ctzll(zm);
                     zm &= zm - 1;
@@ -196,10 +196,11 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
             const int r = r0 + slot;
             const int64_t en = base + r;
             int32_t j;
-            float g;
+            float g, wsel = 0.0f;
             if (ellrow) {
                 j = __shfl(jrow, r & 63, 64);
                 g = __shfl(grow, r & 63, 64);
+                if (recs_on) wsel = __shfl(wlane, r & 63, 64);
                 if (r >= cnt) { j = -1; g = 0.0f; }
             } else {
                 j = r < cnt ? idx[en] : -1;
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_kernel(
             }
             bool stored = false;
             if constexpr (VEC == 4) {
-                if (recs_on && actv) {                               // (an active entry has w != 0: it has a record)
+                if (recs_on && actv && wsel != 0.0f) {               // (an entry has a record iff w != 0; an active one without takes the atomics below)
                     const int rp = recpos[i * 64 + r];
                     if (rp >= 0 && rp < dz_rows) {
                         *reinterpret_cast<float4 *>(dz_rec + (int64_t)rp * hw + o0) = make_float4(dzv[0], dzv[1], dzv[2], dzv[3]);
@@ -450,7 +451,8 @@ int dgg_edge_mlp_bwd_det(const float *AB, int64_t N, int hw, int64_t row0, int64
 // dgg_edge_mlp_bwd for an ELL block whose PAYLOAD PARTITION is at hand (dgg_partp_build of (idx, w) with the entry -> record map:
 // dgg_partp_has_map(N)): the neighbour-side sums d B_j without float atomics -- the row kernel stores every selected entry's d z as a
 // row of dz_rec in record order, edge_mlp_colsum adds each destination node's (consecutive) rows.  w [N,K]: the weights the partition
-// was built from; dz_rec: dz_rows * hw floats of scratch, dz_rows >= the number of records (e.g. the number of candidate edges).
+// was built from (a selected entry with w == 0 has no record: its cotangent goes to dAB by float atomics); dz_rec: dz_rows * hw floats
+// of scratch, dz_rows >= the number of records (e.g. the number of candidate edges).
 // hw a multiple of 4 (power-of-two lane groups), K <= 64; otherwise as dgg_edge_mlp_bwd.
 int dgg_edge_mlp_bwd_partp(const float *AB, int64_t N, int hw, const int32_t *idx, const int32_t *eid, const float *val, const float *dval,
                            const float *w, int K, const float *deg, const float *ex, const float *wdu, const float *wdv, const float *wex,
