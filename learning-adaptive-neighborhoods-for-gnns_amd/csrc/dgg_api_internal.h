@@ -3,12 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define DGG_OK 0
-#define DGG_ERR_ARG 1          // invalid argument (reference style: bare assert, dgm.py:1187-1188)
-#define DGG_ERR_UNSUPPORTED 2  // shape/mode outside what the kernels implement (reference: Exception("mode not found"), dgm.py:1727)
-#define DGG_ERR_HIP 3          // a HIP runtime call or kernel launch failed
+// the public C ABI (error codes, every extern "C" entry point): each definition is compiled against its public declaration
+#include "../../include/dgg_hip.h"
 
-#define DGG_CHUNK_MAXM 32       // chunked rows, ranked search with register lists: at most 32 chunks of 64 ranks per row (2048 ranks)
+#define DGG_CHUNK_MAXM 32      // chunked rows, ranked search with register lists: at most 32 chunks of 64 ranks per row (2048 ranks)
 #define DGG_CHUNK_MAXM_ANY (1 << 20)   // chunked rows of ANY width (dgg_topk_anywide.hip: threshold buffers in memory): up to 2^26 ranks
 
 int dgg_set_error(int code, const char *msg);
@@ -44,7 +42,6 @@ int dgg_allpairs_topk_ranked_impl(const float *xp, int64_t N, int h, int64_t row
 const int *dgg_part_slotmap(const void *part_ws, int64_t rows, int K, int64_t ncols);
 int dgg_norm_da_cols_impl(const void *part_ws, int64_t rows, int K, int64_t ncols, const float *coef_ws, float *da,
                           hipStream_t st);
-extern "C" size_t dgg_part_ws_bytes(int64_t rows, int K, int64_t ncols);
 // payload partition (dgg_scatter.hip): nodeptr [ncols + 1] and the entry -> record map recpos [rows * 64] inside a built workspace
 // (0 on success; recpos is there only when dgg_partp_has_map(rows))
 int dgg_partp_internal_ptrs(const void *partp_ws, int64_t rows, int K, int64_t ncols, const int **nodeptr, const int **recpos);

@@ -1,14 +1,18 @@
 """CPU-side checks: the C-ABI library loads and exports every symbol include/dgg_hip.h declares (no compute
 calls without a GPU); the drop-in modules keep the reference's state_dict contract; ops refuse CPU tensors."""
 import ctypes
+import json
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import ROOT, load_fixture
+from helpers import GOLDEN, ROOT, load_fixture
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 def declared_symbols():
@@ -27,6 +31,61 @@ def test_library_exports_every_declared_symbol():
     # the ctypes prototype table covers the same set (minus the two info functions)
     assert set(dgg_amd._lib.PROTOTYPES) | {"dgg_last_error", "dgg_abi_version"} == set(syms)
     assert dgg_amd._lib.lib().dgg_abi_version() == 6
+
+
+REBUMP = ("a prototype of include/dgg_hip.h changed: bump dgg_abi_version (dgg_capi.hip) and re-record the fixture "
+          "under the new version with tools/record_abi.py")
+
+
+def abi_fixture():
+    with open(os.path.join(GOLDEN, "abi_v6.json")) as f:
+        return json.load(f)
+
+
+def test_header_derived_prototypes_equal_the_recorded_abi():
+    """tests/golden/abi_v6.json was recorded (tools/record_abi.py) from the hand-written ctypes table that preceded the header parser:
+    the tables parsed from include/dgg_hip.h, and what lib() binds from them, are that table, function by function"""
+    import dgg_amd
+    import record_abi as R
+    want = abi_fixture()["functions"]
+    L = dgg_amd._lib
+    assert set(L.PROTOTYPES) == set(L.RESTYPES) == set(want), REBUMP
+    for name, rec in want.items():
+        assert R.encode(L.RESTYPES[name], L.PROTOTYPES[name]) == rec, f"{name}: {REBUMP}"
+    assert R.table()["functions"] == want, REBUMP
+
+
+def test_recorded_abi_is_of_this_abi_version():
+    import dgg_amd
+    assert abi_fixture()["abi_version"] == dgg_amd._lib.lib().dgg_abi_version(), REBUMP
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    """never a guess: a parameter or return type outside the parser's list, or a declaration it cannot take apart, raises and names it"""
+    from dgg_amd import _lib
+    ok = _lib.parse_header("/* c */\n#define X 1\nsize_t dgg_a(const float *const *x, int64_t n, uint32_t s, float t, size_t b, int *o);\nint dgg_b(void);")
+    C = ctypes
+    assert ok == {"dgg_a": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_uint32, C.c_float, C.c_size_t, C.c_void_p]), "dgg_b": (C.c_int, [])}
+    with pytest.raises(_lib.DggHipError, match=r"double y.*dgg_bad"):
+        _lib.parse_header("int dgg_bad(const float *x, double y, void *stream);")
+    with pytest.raises(_lib.DggHipError, match=r"unsigned int n.*dgg_bad"):
+        _lib.parse_header("int dgg_bad(unsigned int n);")
+    with pytest.raises(_lib.DggHipError, match=r"'float'.*dgg_bad"):
+        _lib.parse_header("float dgg_bad(int n);")
+    with pytest.raises(_lib.DggHipError, match="not of the form"):
+        _lib.parse_header("int dgg_good(int n);\nint dgg_bad(void (*cb)(int), int n);")
+
+
+def test_header_constants_equal_the_ops_constants():
+    """every DGG_NOISE_* / DGG_ACT_* / DGG_MODE_* of the header is the like-named constant of ops.py (MODE_HARD_ST is ops-only)"""
+    from dgg_amd import ops
+    txt = open(os.path.join(ROOT, "include", "dgg_hip.h")).read()
+    defs = dict(re.findall(r"^#define DGG_((?:NOISE|ACT|MODE)_\w+)\s+(\d+)\b", txt, flags=re.M))
+    assert sorted(defs) == sorted(["NOISE_NONE", "NOISE_EXPLICIT", "NOISE_HASH", "NOISE_HASH_SYM", "NOISE_RANKED", "NOISE_RANKED_SYM",
+                                   "ACT_NONE", "ACT_LEAKY", "ACT_RELU", "MODE_K_TIMES_EDGE_PROB", "MODE_K_ONLY"])
+    for name, value in defs.items():
+        assert getattr(ops, name) == int(value), name
+    assert ops.MODE_HARD_ST == 3 and "MODE_HARD_ST" not in defs
 
 
 def test_public_header_is_valid_c():

@@ -19,11 +19,7 @@ ENTRIES = ("dgg_allpairs_mlp_topk", "dgg_allpairs_mlp_topk_prior", "dgg_allpairs
 class Baseline:
     def __init__(self, path):
         self.tree = _lib.lib()
-        self.base = ctypes.CDLL(path)
-        for name in ENTRIES:
-            fn = getattr(self.base, name)
-            fn.argtypes = _lib.PROTOTYPES[name]
-            fn.restype = ctypes.c_int
+        self.base = _lib.bind(ctypes.CDLL(path), ENTRIES)
 
     def __getattr__(self, name):                                # (every other symbol stays the tree's)
         return getattr(self.base if name in ENTRIES else self.tree, name)
