@@ -1,0 +1,56 @@
+/* dgg_hip_next.h -- entry points of libdgg_hip.so added SINCE ABI v6.
+ *
+ * include/dgg_hip.h is the recorded ABI (dgg_abi_version() == 6): its prototypes do not change between bumps.  What the library has
+ * gained since is declared here.  The header is purely additive -- it changes no declaration of dgg_hip.h, which it includes, and every
+ * entry point keeps that header's conventions (int return: DGG_OK or a DGG_ERR_* code with dgg_last_error(); device pointers; `stream` a
+ * hipStream_t) -- and it is folded into dgg_hip.h at the next ABI bump.  The library's definitions are compiled against this file and the
+ * ctypes binding parses it into tables of its own (dgg_amd._lib.NEXT_PROTOTYPES / NEXT_RESTYPES).
+ */
+#ifndef DGG_HIP_NEXT_H
+#define DGG_HIP_NEXT_H
+#include "dgg_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- edge-list candidates on CHUNKED rows (rows of any width) --------------------------------------------------------------------
+ * The live class takes the candidates of row i from the stored entries of in_adj (dgm.py:1613-1623), perturbs them (dgm.py:1211-1229)
+ * and ramps over the whole sorted row with an unbounded learned degree (select_top_k, dgm.py:1402-1421).  dgg_edgelist_topk_softk keeps
+ * the 64 best candidates of a row, exact while k_i + 8.5 <= 64 or the row has no more candidates than that; here row i keeps its
+ * L_i = min(n_i, ceil(k_i + 8.5) + 1) best candidates (n_i = its candidates: every rank that can carry weight) in the chunks
+ * [cptr[i], cptr[i+1]) of idx / val / w [ccap,64], rank r at entry r % 64 of chunk r / 64 (dgg_hip.h, "CHUNKED rows").
+ * cptr [row1-row0+1] = dgg_chunk_layout of the CLAMPED degrees min(k_i, n_i - 9.5), which gives exactly ceil(L_i / 64) chunks per row (a
+ * row of 3 candidates with k = 1000 owns one chunk); k [row1-row0] stays the TRUE learned degree: the ramp and every backward read it.
+ * rowptr [row1-row0+1] / col: the rebased CSR slice of the rows asked for with global columns, xp [N,h] every node, the noise keyed on
+ * the global pair (row0 + i, j) -- as dgg_edgelist_topk_softk_rows.  noise_mode DGG_NOISE_NONE / HASH / HASH_SYM (an explicit noise
+ * tensor is outside the fused layer).  One wavefront per row; score chain, key order (score descending, lower column first) and bits of
+ * dgg_edgelist_topk_softk[_rows] at h in {16, 32, 64, 128}: with every M_i = 1 the ranks below L_i are its output at K = 64.
+ * w = the ramp of dgg_allpairs_topk_ranked_wide (mode 0 score x ramp, 1 the ramp, 3 the straight-through forward value); rs [row1-row0] =
+ * lane-wise sums over a row's chunks in chunk order, then the wavefront butterfly -- a one-chunk row sums as dgg_edgelist_topk_softk does.
+ * Every other slot of a row's chunks and every chunk in [cptr[rows], ccap) is written EMPTY (idx -1, val 0, w 0); nothing outside the
+ * arrays is written.  A wavefront settles 8 chunks of a row per pass over its candidates; rows of more chunks take ceil(maxm / 8)
+ * passes launched from the host integer maxm >= max M_i (no device read-back), each continuing strictly below the last key the previous
+ * one wrote.
+ * DGG_ERR_UNSUPPORTED and nothing written: h outside {16, 32, 64, 128} or xp not 16-byte aligned, a noise_mode other than 0 / 2 / 3.
+ * DGG_ERR_ARG and nothing written: mode outside {0, 1, 3}, rows outside 0 <= row0 <= row1 <= N < 2^31, maxm outside 1..2^20, ccap
+ * outside 0 <= ccap < 2^25, a NULL array.  row0 == row1 returns 0 without a launch. */
+int dgg_edgelist_topk_chunked(const float *xp, int64_t N, int h, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                              float t, int noise_mode, uint32_t s0, uint32_t s1, const float *k, int mode, int maxm, const int32_t *cptr,
+                              int64_t ccap, int32_t *idx, float *val, float *w, float *rs, void *stream);
+/* The same from given edge probabilities p_edge [E] (CSR order of the slice, the columns of a row ascending): the edge-MLP scorers' path
+ * (dgm.py:1628-1725 through dgg_edge_mlp_fwd), in place of dgg_edgelist_topk_p[_rows] + dgg_softk_fwd.  Perturbation and key order are
+ * dgg_edgelist_topk_p's (dgm.py:1211-1229, 1404; ties: the earlier candidate of the row first); ramp, row sums, empty slots, passes and
+ * layout as above (dgm.py:1402-1421).  ex_edge (nullable, [E]): the per-candidate extra -- the stored value a_uv of u-v-A_uv / A_uv, or
+ * the distance extra dgg_edge_mlp_fwd returned -- gathered to ex_out [ccap,64] per kept slot, 0 on empty slots (ex_out is required with
+ * ex_edge and ignored without).  eid (nullable, [ccap,64]): the kept candidate's index in the slice's per-edge arrays, -1 on empty slots.
+ * Refusals as above (there is no latent width here: p_edge is already the score). */
+int dgg_edgelist_topk_p_chunked(const float *p_edge, int64_t N, int64_t row0, int64_t row1, const int64_t *rowptr, const int32_t *col,
+                                int noise_mode, uint32_t s0, uint32_t s1, const float *k, int mode, int maxm, const int32_t *cptr,
+                                int64_t ccap, const float *ex_edge, int32_t *idx, float *val, float *ex_out, int32_t *eid, float *w,
+                                float *rs, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DGG_HIP_NEXT_H */

@@ -1,6 +1,8 @@
 """ctypes binding of libdgg_hip.so.  The prototypes are not written here: PROTOTYPES / RESTYPES are parsed from the public header
-include/dgg_hip.h, the one description of the C ABI (the library's definitions are compiled against the same file).  Fails loudly when
-the HIP library or the header is missing: there is no CPU fallback anywhere in this package."""
+include/dgg_hip.h, the one description of the C ABI (the library's definitions are compiled against the same file).  Entry points added
+since that ABI version was recorded are declared in include/dgg_hip_next.h (purely additive, folded into dgg_hip.h at the next ABI bump)
+and parsed into tables of their own, NEXT_PROTOTYPES / NEXT_RESTYPES: PROTOTYPES stays the recorded ABI.  Fails loudly when the HIP
+library or a header is missing: there is no CPU fallback anywhere in this package."""
 import ctypes as C
 import os
 import re
@@ -9,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("DGG_HIP_SO", os.path.join(_HERE, "libdgg_hip.so"))   # override: diagnostic builds only
 
 HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip.h"))
+NEXT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_next.h"))     # entry points since the recorded ABI
 
 _C_TYPES = {"int": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float, "size_t": C.c_size_t}
 _C_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -19,7 +22,7 @@ class DggHipError(RuntimeError):
     pass
 
 
-def parse_header(text):
+def parse_header(text, where=HEADER):
     """C declarations `ret dgg_name(params);` -> {name: (restype, [argtypes])}.  Any pointer is a c_void_p; a type outside _C_TYPES /
     _C_RETURNS is an error naming the declaration, never a guess."""
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -29,7 +32,7 @@ def parse_header(text):
         decl = " ".join(f"{ret}{name}({params})".split())
         ret = " ".join(ret.split())
         if ret not in _C_RETURNS:
-            raise DggHipError(f"{HEADER}: return type {ret!r} has no ctypes mapping: {decl}")
+            raise DggHipError(f"{where}: return type {ret!r} has no ctypes mapping: {decl}")
         argtypes = []
         for param in ([] if params.strip() == "void" else params.split(",")):
             words = [w for w in param.split() if w != "const"]             # `type name` or a bare `type`
@@ -38,32 +41,39 @@ def parse_header(text):
             elif len(words) in (1, 2) and words[0] in _C_TYPES:
                 argtypes.append(_C_TYPES[words[0]])
             else:
-                raise DggHipError(f"{HEADER}: parameter {' '.join(param.split())!r} has no ctypes mapping: {decl}")
+                raise DggHipError(f"{where}: parameter {' '.join(param.split())!r} has no ctypes mapping: {decl}")
         decls[name] = (_C_RETURNS[ret], argtypes)
     if len(decls) != len(set(re.findall(r"\b(dgg_\w+)\s*\(", text))):
-        raise DggHipError(f"{HEADER}: a dgg_* declaration is not of the form `ret dgg_name(params);`")
+        raise DggHipError(f"{where}: a dgg_* declaration is not of the form `ret dgg_name(params);`")
     return decls
 
 
-def _read_header():
-    if not os.path.exists(HEADER):
-        raise DggHipError(f"{HEADER} is missing: the ctypes prototypes are read from the public header")
-    with open(HEADER) as f:
-        return parse_header(f.read())
+def _read_header(path=HEADER):
+    if not os.path.exists(path):
+        raise DggHipError(f"{path} is missing: the ctypes prototypes are read from the public header")
+    with open(path) as f:
+        return parse_header(f.read(), path)
 
 
 _DECLS = _read_header()
 PROTOTYPES = {name: argtypes for name, (_, argtypes) in _DECLS.items() if name not in _INFO}    # name -> argtypes
 RESTYPES = {name: restype for name, (restype, _) in _DECLS.items() if name not in _INFO}        # name -> restype
+_NEXT_DECLS = _read_header(NEXT_HEADER)
+NEXT_PROTOTYPES = {name: argtypes for name, (_, argtypes) in _NEXT_DECLS.items()}               # the same two tables for the entry
+NEXT_RESTYPES = {name: restype for name, (restype, _) in _NEXT_DECLS.items()}                   # points of dgg_hip_next.h
+if set(_NEXT_DECLS) & set(_DECLS):
+    raise DggHipError(f"{NEXT_HEADER} declares again what {HEADER} declares: {sorted(set(_NEXT_DECLS) & set(_DECLS))}")
 
 _lib = None
 
 
 def bind(L, names=None):
-    """Gives the entry points `names` (default: every declared one) of the CDLL handle L the header's argtypes and restype."""
-    for name in (_DECLS if names is None else names):
+    """Gives the entry points `names` (default: every declared one, of both headers) of the CDLL handle L the headers' argtypes and
+    restype."""
+    decls = {**_DECLS, **_NEXT_DECLS}
+    for name in (decls if names is None else names):
         fn = getattr(L, name)      # AttributeError if the library does not export a declared symbol
-        fn.restype, fn.argtypes = _DECLS[name]
+        fn.restype, fn.argtypes = decls[name]
     return L
 
 

@@ -749,21 +749,26 @@ class DGG_LearnableK_debug(nn.Module):
         if why is not None:
             return self._fused_fallback(why)
         N = x.shape[0]
-        mlp_mode, wide_state = getattr(self._scorer(), "fused", False), None
+        mlp_mode, wide_state, el_wide = getattr(self._scorer(), "fused", False), None, False
         in_adj, cand, deg, _, _, _ = self._candidates(in_adj)
         if cand is None:
             # (args.dgg_wide_rows is u-v-dist's: the edge-MLP scorers have args.dgg_allpairs_mlp_rows, and no CSR form on all pairs)
             if not mlp_mode and (self.__dict__.get("_ap_wide", {}).get("on") or self._allpairs_csr_plan(N) == "csr"):
                 return None                                   # (policy "csr": every column ranked, the modules' CSR form)
         else:
+            # (args.dgg_edgelist_rows = "chunked": rows of any width stay here, as chunked rows -- el_wide: they are live in this
+            #  forward.  A graph whose rows all fit the list, and a hipGraph capture -- nothing can be read back: the list and its
+            #  enforced bound -- run exactly as under "list")
+            el_chunked = self._edgelist_chunked()
             wide_state = self._wide_rows_state(in_adj, cand[0])
-            if wide_state is True:                            # (known before any kernel runs: this graph takes the CSR form -- no discarded forward)
+            el_wide = el_chunked and wide_state is not False and not _capturing()
+            if wide_state is True and not el_wide:         # (known before any kernel runs: this graph takes the CSR form -- no discarded forward)
                 return self._fused_fallback("rows wider than the list with learned degrees beyond it (CSR form)")
         mlp, sc_static = self._fused_scorer(in_adj) if mlp_mode else (None, None)
         layer = self.__dict__.get("_fused_layer") if engine is None else engine
         if engine is None and (layer is None or layer.N != N):
             layer = self.__dict__["_fused_layer"] = ShardedDGGConv(ops, N, K=64, t=ops.T_DIST)
-        noise_mode, chunk_active = self._fused_configure(layer, x, cand, wide_state, mlp_mode)
+        noise_mode, chunk_active = self._fused_configure(layer, x, cand, wide_state, mlp_mode, el_wide=el_wide)
         kn = self.k_net
         params = (self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias, self.node_encode_for_k[0].weight,
                   self.node_encode_for_k[0].bias, self.k_embed[0].weight, self.k_embed[0].bias, kn.k_mu.weight, kn.k_mu.bias,
@@ -774,7 +779,7 @@ class DGG_LearnableK_debug(nn.Module):
             Z, ahat = _FusedDGGMlpConvFn.apply(x, deg, layer, sc_static, *_sc_terms(mlp), *params)
         else:
             Z, ahat = _FusedDGGConvFn.apply(x, deg, layer, *params)       # (ops.ChunkCapacityError: a learned degree is NaN)
-        return self._fused_result(layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm)
+        return self._fused_result(layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm, el_wide=el_wide)
 
     def _fused_outside(self, x, in_adj, conv_weight):
         """-> the reason this configuration is outside the fused layer, or None.  Which clause sends a forward to the separate modules
@@ -836,9 +841,10 @@ class DGG_LearnableK_debug(nn.Module):
             static["prior"] = prior
         return mlp, static
 
-    def _fused_configure(self, layer, x, cand, wide_state, mlp_mode):
+    def _fused_configure(self, layer, x, cand, wide_state, mlp_mode, el_wide=False):
         """sets the engine up for this forward: noise generator, selection mode, what rows wider than 64 ranks do, device flags
-        -> (noise_mode, chunk_active = this forward reads its chunk layout back)"""
+        -> (noise_mode, chunk_active = this forward reads its chunk layout back).  el_wide: edge-list candidates with rows wider than the
+        list under args.dgg_edgelist_rows = "chunked" (not capturing): the engine lays the rows' clamped degrees out on every forward"""
         a, N = self.args, x.shape[0]
         ap_mlp = cand is None and mlp_mode                    # edge-MLP scorer on all-pairs candidates: every pair is scored, as on edge lists
         noise_mode, _, seed = self._noise_now(x, cand is None, ap_mlp)
@@ -863,7 +869,7 @@ class DGG_LearnableK_debug(nn.Module):
         # all-pairs rows wider than the 64-rank list (learned degrees k_i + 9.5 > 64): chunked rows inside the engine, from the forward
         # that first needs them (one readback of the chunk count per forward; a hipGraph capture replays the last eager layout)
         chunked = cand is None and self._chunk_policy(noise_mode)
-        layer.wide_rows, layer.wide_cap = ("auto" if chunked else "off"), None
+        layer.wide_rows, layer.wide_cap = ("auto" if (chunked or el_wide) else "off"), None
         if chunked and _capturing():
             # nothing can be read back under capture: the layout of the last eager forward on this module, with some slack, becomes a
             # FIXED capacity whose overflow flags check_ell_bound() reads; no wide row then: the list, with its enforced bound
@@ -871,7 +877,9 @@ class DGG_LearnableK_debug(nn.Module):
             layer.wide_cap = None if last is None or last[0] == N else (last[0] + last[0] // 8 + 64, min(ops.chunk_maxm_for(N), last[1] + max(1, last[1] // 8)))
             if layer.wide_cap is None:
                 layer.wide_rows = "off"
-        if cand is not None and not mlp_mode:                 # the ELL-width bound is tested inside the search kernel (no extra launches)
+        if el_wide:                                           # every weighted rank is kept: there is no bound to test, and no flag
+            layer.overflow = None
+        elif cand is not None and not mlp_mode:               # the ELL-width bound is tested inside the search kernel (no extra launches)
             # (a forward whose fate is decided from its own learned degrees -- wide_state None -- raises a SCRATCH flag: if it is
             #  discarded for the CSR form its flag must not reach check_ell_bound, and flags of earlier forwards must survive it)
             name = "_overflow_scratch" if (wide_state is None and not _capturing()) else "_overflow_dev"
@@ -881,9 +889,10 @@ class DGG_LearnableK_debug(nn.Module):
             layer.overflow = flag
         return noise_mode, chunked and layer.wide_rows == "auto" and layer.wide_cap is None
 
-    def _fused_result(self, layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm):
+    def _fused_result(self, layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm, el_wide=False):
         """after the node ran: generator status, what this forward's learned degrees decide (CSR form from here on / overflow flags),
-        and the returned adjacencies"""
+        and the returned adjacencies.  el_wide (_fused_configure): chunked edge-list rows kept every weighted rank -- nothing is decided
+        from the learned degrees and no overflow is tracked"""
         st, N = layer.saved, layer.N
         if noise_mode == ops.NOISE_RANKED_SYM:                # the reference's DEFAULT noise (symmetric_noise=True, dgm.py:1216-1223): the
             self._note_rsym(layer.rsym_last, N)     # generator's status words, checked by check_ell_bound as for the modules
@@ -892,7 +901,7 @@ class DGG_LearnableK_debug(nn.Module):
         if st.get("partp") is None:                           # (shape outside the partitioned backward: the separate modules)
             return self._fused_fallback("shape outside the partitioned backward")
         k = st["k"]
-        if cand is not None and self._wide_rows(in_adj, cand[0], k, layer):
+        if cand is not None and not el_wide and self._wide_rows(in_adj, cand[0], k, layer):
             # rows wider than the ELL with learned degrees beyond it: the CSR form from here on (this forward is discarded, once per graph)
             if not mlp_mode and "_overflow_scratch" in self.__dict__:
                 self._overflow_scratch.zero_()
@@ -903,6 +912,8 @@ class DGG_LearnableK_debug(nn.Module):
         if cand is None and lay is None and not chunk_active:
             self._track_overflow(k, None)
         elif cand is None and layer.wide_cap is not None:     # fixed capacity (capture): overflow flags in layer.wide_sticky (check_ell_bound)
+            pass
+        elif el_wide:
             pass
         elif mlp_mode and cand is not None:
             ent = self.__dict__.get("_wide_cache", {}).get(id(in_adj))
@@ -975,7 +986,9 @@ class DGG_LearnableK_debug(nn.Module):
     def wide_row_plan(self, N, all_pairs, noise_mode):
         """What rows that need more than 64 ranks do for a graph of N nodes under args.dgg_wide_rows -- the ONE summary of the policy
         (the predicates the forwards use: _chunk_policy, _wide_rows_state, _allpairs_wide):
-          "chunked"          all-pairs candidates: ceil(k_i + 8.5) + 1 ranks of every row in chunks of 64, any width (auto / chunked;
+          "chunked"          edge-list candidates under args.dgg_edgelist_rows = "chunked" (_edgelist_chunked: the fused layer keeps rows
+                             of any width; the separate modules keep the CSR form);
+                             all-pairs candidates: ceil(k_i + 8.5) + 1 ranks of every row in chunks of 64, any width (auto / chunked;
                              the edge-MLP scorers: with args.dgg_allpairs_mlp_rows = "chunked", whatever args.dgg_wide_rows says --
                              a captured forward keeps the list and its enforced bound although the answer here is "chunked")
           "csr"              the CSR form of select_top_k from the first forward (csr)
@@ -986,6 +999,8 @@ class DGG_LearnableK_debug(nn.Module):
         Which node runs each row form: the route table of DESIGN.md section 5."""
         policy = getattr(self.args, "dgg_wide_rows", "auto")
         if not all_pairs:
+            if self._edgelist_chunked():
+                return "chunked"
             return {"ell": "list", "csr": "csr"}.get(policy, "csr_when_needed")
         if self._chunk_policy(noise_mode):
             return "chunked"
@@ -1012,6 +1027,26 @@ class DGG_LearnableK_debug(nn.Module):
             raise ValueError(f"args.dgg_allpairs_mlp_rows must be 'list' or 'chunked', not {rows!r}")
         if rows == "chunked" and self.ell_width != 64:
             raise ValueError(f"args.dgg_allpairs_mlp_rows = 'chunked' needs args.dgg_ell_width = 64 (chunks of 64 ranks), not {self.ell_width}")
+        return rows == "chunked"
+
+    def _edgelist_chunked(self):
+        """Edge-list rows wider than the 64-rank list as chunked rows inside the fused layer (u-v-dist and the edge-MLP scorers; no / hash /
+        symmetric hash noise; k_times_edge_prob and k_only)?
+        args.dgg_edgelist_rows: "list" (default: the 64-rank list; rows that outgrow it leave for the CSR form under args.dgg_wide_rows =
+        "auto", once per graph and for good) / "chunked" (row i keeps its min(n_i, ceil(k_i + 8.5) + 1) weighted ranks in chunks of 64:
+        dgg_edgelist_topk_chunked / dgg_edgelist_topk_p_chunked; one layout read-back per forward on graphs that have a row wider than
+        the list, none on the others).  "chunked" needs the full list width (args.dgg_ell_width = 64: a chunk is 64 ranks) and
+        args.dgg_wide_rows "auto" / "chunked" ("ell" / "csr" / "csr_auto" ask for another row form); anything else raises.  Under a
+        hipGraph capture nothing can be read back: the list and its bound stay.  The separate modules (forward) keep the CSR form."""
+        rows = getattr(self.args, "dgg_edgelist_rows", "list")
+        if rows not in ("list", "chunked"):
+            raise ValueError(f"args.dgg_edgelist_rows must be 'list' or 'chunked', not {rows!r}")
+        if rows == "chunked" and self.ell_width != 64:
+            raise ValueError(f"args.dgg_edgelist_rows = 'chunked' needs args.dgg_ell_width = 64 (chunks of 64 ranks), not {self.ell_width}")
+        policy = getattr(self.args, "dgg_wide_rows", "auto")
+        if rows == "chunked" and policy not in ("auto", "chunked"):
+            raise ValueError(f"args.dgg_edgelist_rows = 'chunked' needs args.dgg_wide_rows = 'auto' or 'chunked', not {policy!r} (which asks for "
+                             "another form of the rows wider than the list)")
         return rows == "chunked"
 
     @staticmethod

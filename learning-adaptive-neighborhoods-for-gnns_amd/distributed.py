@@ -31,7 +31,12 @@ Edge-list rows wider than the 64-rank list whose learned degree needs more ranks
 (DGG_LearnableK_debug._csr_soft_adjacency -> CsrAdjacency.normalize -> GCNConv on a CsrAdjacency), on one GPU and, as an OPT-IN, on a row
 shard: args.dgg_wide_rows = "csr" (the CSR form from the first forward) or "csr_auto" (the fused layer until the collective wide-row flag
 first fires, the CSR form for that forward -- recomputed -- and every later one on that graph).  Under the default "auto" such a forward
-still raises NotImplementedError on every rank at once (the flag is ORed over the ranks).  The sharded CSR form (_CsrForm) keeps the
+still raises NotImplementedError on every rank at once (the flag is ORed over the ranks).  Under args.dgg_edgelist_rows = "chunked"
+(opt-in; with args.dgg_wide_rows "auto" / "chunked") such rows never leave the fused layer, on one GPU or on a row shard: every rank lays the
+clamped degrees min(k_i, n_i - 9.5) of its own rows out in chunks of 64 ranks (one read-back of the chunk count per forward and rank, no
+collective: edge lists draw the per-pair hash keyed on global ids) and ranks them with dgg_edgelist_topk_chunked /
+dgg_edgelist_topk_p_chunked; the adjacency returned carries `layout`, and neither the sticky CSR decision nor that NotImplementedError
+applies.  The sharded CSR form (_CsrForm) keeps the
 one-GPU operation order, so its forward has the one-GPU bits: every rank computes the projection, the edge-MLP scorer's per-node products
 and the k-net on the whole graph (the k-net normalises with the mean and std of all N prior degrees), scores its own rows' entries
 through the _rows entries of the dgg_csr_* kernels (noise keyed on the global pair), and the step costs, beside the loss's scalar: two
@@ -241,7 +246,8 @@ class ShardedGCN_DGG(nn.Module):
     Every rank must draw the same noise: seed the CPU generator identically on every rank (torch.manual_seed) or call
     model.dggs[0].set_seed.  The dropout between the layers draws each rank's mask from its own CUDA generator.
     Outside its coverage the wrapper raises (no silent fall-back), before any collective: on several ranks, edge-list candidates whose
-    rows need the CSR form under the default args.dgg_wide_rows = 'auto' (raised by every rank in the same forward), a writer, configurations the fused layer declines, a hipGraph capture on several ranks, args.dgg_hard_literal,
+    rows need the CSR form under the default args.dgg_wide_rows = 'auto' and args.dgg_edgelist_rows = 'list' (raised by every rank in the
+    same forward; args.dgg_edgelist_rows = 'chunked' keeps such rows in the fused layer as chunked rows), a writer, configurations the fused layer declines, a hipGraph capture on several ranks, args.dgg_hard_literal,
     args.dgg_differentiable_adj, args.dgg_wide_rows other than 'auto' / 'chunked' (edge lists on several ranks: or 'csr' / 'csr_auto'), and on several ranks args.dgg_sym_generator = 'auto'
     (a generator switch decided from one rank's rows)."""
 
@@ -310,6 +316,7 @@ class ShardedGCN_DGG(nn.Module):
             if policy not in ("auto", "chunked") + _SHARDED_CSR_POLICIES:
                 raise NotImplementedError(f"{what}: args.dgg_wide_rows = {policy!r} (a row shard keeps the 64-rank list, or takes the CSR "
                                           "form of rows wider than it under 'csr' / 'csr_auto')")
+            dgg._edgelist_chunked()                          # (args.dgg_edgelist_rows: an unknown value or a combination it refuses raises)
             why = dgg._fused_outside(x, in_adj, m.conv1.W)
             if why is not None:
                 raise NotImplementedError(f"{what}: the fused layer does not cover this configuration ({why})")
@@ -354,7 +361,8 @@ class ShardedGCN_DGG(nn.Module):
             # (decided collectively: _wide_rows ORs the ranks' flags, so every rank raises here in the same forward)
             raise NotImplementedError("ShardedGCN_DGG (edge-list candidates on several ranks): a row wider than the 64-rank list has a "
                                       "learned degree beyond it; the CSR form of such rows is not sharded under args.dgg_wide_rows = "
-                                      f"{policy!r} (opt in with 'csr' or 'csr_auto') ({m.dggs[0].__dict__.get('fused_fallback', {})})")
+                                      f"{policy!r} (opt in with 'csr' or 'csr_auto', or keep such rows in the fused layer as chunked rows "
+                                      f"with args.dgg_edgelist_rows = 'chunked') ({m.dggs[0].__dict__.get('fused_fallback', {})})")
         if got is None:
             raise NotImplementedError("ShardedGCN_DGG: this forward left the fused layer's coverage "
                                       f"({m.dggs[0].__dict__.get('fused_fallback', {})})")

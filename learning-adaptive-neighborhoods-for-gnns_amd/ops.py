@@ -598,6 +598,80 @@ def edgelist_topk_softk(xp, rowptr, col, k, mode=MODE_K_TIMES_EDGE_PROB, K=DEFAU
     return idx, val, w, rs
 
 
+def edgelist_clamped_degrees(k, rowptr):
+    """the degrees the chunk layout of EDGE-LIST rows is run on: min(k_i, n_i - 9.5), n_i = the row's candidates.  chunk_layout then gives
+    row i exactly ceil(L_i / 64) chunks for L_i = min(n_i, ceil(k_i + 8.5) + 1), the ranks that can carry weight (a row of 3 candidates
+    with k = 1000 gets one chunk, not 16).  The search, the ramp and every backward take the TRUE k."""
+    lens = (rowptr[1:] - rowptr[:-1]).to(torch.float32)
+    return torch.minimum(_chk(k), lens - 9.5)
+
+
+def _chunked_outputs(layout, n, dev, out, nflat):
+    """the [chunks,64] outputs of the chunked edge-list searches + rs [n]: fresh, or the caller's (tests: canaried buffers of any capacity
+    >= layout.chunks; the spare chunks come back empty) -> tensors, capacity"""
+    if out is not None:
+        assert out[0].shape[0] >= layout.chunks
+        return out, out[0].shape[0]
+    C_ = layout.chunks
+    mk = lambda dt: torch.empty((C_, 64), device=dev, dtype=dt)  # noqa: E731
+    return tuple(None if dt is None else mk(dt) for dt in nflat) + (torch.empty((n,), device=dev, dtype=torch.float32),), C_
+
+
+def edgelist_topk_chunked(xp, rowptr, col, k, layout, mode=MODE_K_TIMES_EDGE_PROB, t=T_DIST, noise_mode=NOISE_NONE, seed=(0, 0), rows=None,
+                          out=None):
+    """edgelist_topk_softk for rows of ANY width, on chunked rows (dgg_edgelist_topk_chunked, include/dgg_hip_next.h): row i keeps its
+    min(n_i, ceil(k_i + 8.5) + 1) best candidates in the chunks of `layout` = chunk_layout(edgelist_clamped_degrees(k, rowptr)), the ramp
+    fused -> idx, val, w [chunks,64], rs [rows]; None when the latent width is not 16 / 32 / 64 / 128.  k: the TRUE learned degrees.
+    noise_mode NOISE_NONE / NOISE_HASH / NOISE_HASH_SYM.  rows = (r0, r1): the rows of a row shard, as edgelist_topk_softk takes them
+    (rebased CSR slice with global columns; k, layout and the outputs are the shard's rows).  out = (idx, val, w, rs): write into these."""
+    xp = _chk(xp)
+    N, h = xp.shape
+    if h not in KERNEL_WIDTHS:
+        return None
+    rowptr, col, k = _chk(rowptr, torch.int64), _chk(col, torch.int32), _chk(k)
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    n = r1 - r0
+    assert rowptr.shape[0] == n + 1 and k.shape[0] == n and layout.rows == n, "edgelist_topk_chunked: rowptr [rows+1], k [rows] and the layout of the rows asked for"
+    (idx, val, w, rs), C_ = _chunked_outputs(layout, n, xp.device, out, (torch.int32, torch.float32, torch.float32))
+    if col.shape[0] == 0:                                # (an empty tensor has no data pointer; no row points into this one)
+        col = torch.zeros((1,), device=xp.device, dtype=torch.int32)
+    pe = _probe_begin()
+    _lib.check(_lib.lib().dgg_edgelist_topk_chunked(_ptr(xp), N, h, r0, r1, _ptr(rowptr), _ptr(col), float(t), int(noise_mode), seed[0], seed[1],
+                                                    _ptr(k), int(mode), layout.maxm, _ptr(layout.cptr), C_, _ptr(idx), _ptr(val), _ptr(w), _ptr(rs),
+                                                    _stream()), "edgelist_topk_chunked")
+    _probe_end("edgelist_topk", pe)
+    return idx, val, w, rs
+
+
+def edgelist_topk_p_chunked(p_edge, N, rowptr, col, k, layout, mode=MODE_K_TIMES_EDGE_PROB, noise_mode=NOISE_NONE, seed=(0, 0), ex_edge=None,
+                            rows=None, out=None):
+    """edgelist_topk_p + softk_fwd for rows of ANY width, on chunked rows (dgg_edgelist_topk_p_chunked): perturbation + ranking of given
+    edge probabilities p_edge [E] into the chunks of `layout` (as edgelist_topk_chunked), the ramp fused -> idx, val, ex, w [chunks,64],
+    rs [rows]; ex = ex_edge [E] (the per-candidate extra: a stored value, or edge_mlp_fwd's distance extra) gathered per kept slot, 0 on
+    empty slots; None without ex_edge.  rows = (r0, r1): as edgelist_topk_p.  out = (idx, val, ex, w, rs, eid): write into these; eid
+    (or None) = the kept candidate's index in the per-edge arrays, -1 on empty slots."""
+    p_edge = _chk(p_edge)
+    rowptr, col, k = _chk(rowptr, torch.int64), _chk(col, torch.int32), _chk(k)
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    n = r1 - r0
+    assert rowptr.shape[0] == n + 1 and k.shape[0] == n and layout.rows == n, "edgelist_topk_p_chunked: rowptr [rows+1], k [rows] and the layout of the rows asked for"
+    eid = None
+    if out is not None:
+        out, eid = tuple(out[:5]), out[5]
+    (idx, val, ex, w, rs), C_ = _chunked_outputs(layout, n, p_edge.device, out,
+                                                 (torch.int32, torch.float32, None if ex_edge is None else torch.float32, torch.float32))
+    assert (ex is None) == (ex_edge is None)
+    if col.shape[0] == 0:                                # (empty tensors have no data pointer; no row points into these)
+        col = torch.zeros((1,), device=p_edge.device, dtype=torch.int32)
+        p_edge = torch.zeros((1,), device=col.device, dtype=torch.float32)
+        ex_edge = None if ex_edge is None else p_edge
+    _lib.check(_lib.lib().dgg_edgelist_topk_p_chunked(_ptr(p_edge), N, r0, r1, _ptr(rowptr), _ptr(col), int(noise_mode), seed[0], seed[1], _ptr(k),
+                                                      int(mode), layout.maxm, _ptr(layout.cptr), C_, _ptr(None if ex_edge is None else _chk(ex_edge)),
+                                                      _ptr(idx), _ptr(val), _ptr(ex), _ptr(eid), _ptr(w), _ptr(rs), _stream()),
+               "edgelist_topk_p_chunked")
+    return idx, val, ex, w, rs
+
+
 def literal_hard_fwd(xp, cand, idx, w, t=T_DIST, noise_mode=NOISE_NONE, G=None, seed=(0, 0), threshold=0.5):
     """the debug class's literal dgg_hard output (dgm.py:1294-1311) from the soft ELL adjacency (idx, w): -> hidx, hval, hsrc [N,K];
     cand = None (all pairs) or (rowptr, col); N <= 8192"""

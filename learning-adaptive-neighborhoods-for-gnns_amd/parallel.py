@@ -157,6 +157,14 @@ class KernelContract:
     def softk_bwd_rows_chunked(self, idx, val, k, rs, dA, da_cols, ahat, layout, row0=0, mode=0):
         return None
 
+    # edge-list candidates on chunked rows (rows of any width): search + ramp of u-v-dist, and perturbation + ranking + ramp of the
+    # edge-MLP scorers' probabilities.  An engine that has laid wide rows out raises when the namespace answers None
+    def edgelist_topk_chunked(self, xp, rowptr, col, k, layout, mode, t, noise_mode, seed, rows=None):
+        return None
+
+    def edgelist_topk_p_chunked(self, p_edge, N, rowptr, col, k, layout, mode, noise_mode, seed, ex_edge=None, rows=None):
+        return None
+
     def rowmin_logp_bound(self, xp, t, rows=None):
         return None
 
@@ -233,6 +241,9 @@ class ShardedDGGConv:
     Edge-list candidates, and an edge-MLP scorer on any candidates, need replicated features (x_full) on several ranks: every rank
     projects xp (and the edge-MLP scorer's AB) for all N nodes, scores its own rows' candidates and sums the scorer's gradients with the
     layer's in one all-reduce.
+    Edge-list rows wider than the 64-rank list whose learned degrees need more keep every weighted rank in chunked rows under
+    wide_rows = "auto" (_chunk_layout_edge_list; edgelist_topk_chunked, or edge_mlp_fwd + edgelist_topk_p_chunked with a scorer) and run
+    the backward of chunked all-pairs rows; the default "off" keeps the list, whose bound the caller enforces.
     An edge-MLP scorer on ALL-PAIRS candidates (u-v-deg / u-v-deg-dist / edge_conv: they read the two end nodes and their prior degrees
     only) scores all N columns of the rank's rows in one kernel (allpairs_mlp_topk; chunked rows under wide_rows: allpairs_mlp_topk_wide)
     under no / hash / symmetric hash noise keyed on the global pair; DESIGN.md has the step's kernel sequence.  u-v-A_uv joins them when
@@ -288,6 +299,7 @@ class ShardedDGGConv:
         self.r0, self.r1, self.per = shard_bounds(N, self.world, self.rank)
         assert cand is None or self.world == 1 or x_full is not None, "edge-list candidates on several ranks: replicated features (x_full)"
         self._cand_cache = None                              # (rows, weakrefs of rowptr / col, their slice): _cand_rows
+        self._lens_cache = None                              # (weakref of the rows' rowptr, their n_i - 9.5): _chunk_layout_edge_list
         self.bufs = {}                                       # collective staging buffers, kept between steps
         # Rows wider than the 64-rank list (all-pairs candidates, ranked noise): the learned degree is unbounded (dgm.py:1580-1584) and
         # the reference ramps over the whole dense row (dgm.py:1402-1421).  wide_rows: "off" = the [rows,64] list whatever k (exact
@@ -352,10 +364,13 @@ class ShardedDGGConv:
                                                      # symmetric per-pair hash -- same law, another realisation; no wide-row form of its own)
 
     def _chunk_layout(self, k):
-        """-> ops.ChunkLayout for this forward's learned degrees, or None: every row fits the 64-rank list (or wide_rows is off)"""
+        """-> ops.ChunkLayout for this forward's learned degrees, or None: every row fits the 64-rank list (or wide_rows is off).
+        Edge-list candidates: _chunk_layout_edge_list"""
         kern = self.kern
-        if self.wide_rows == "off" or self.noise_mode not in self.WIDE_NOISE or self.cand is not None or self.K != 64:
+        if self.wide_rows == "off" or self.noise_mode not in self.WIDE_NOISE or self.K != 64:
             return None
+        if self.cand is not None:
+            return self._chunk_layout_edge_list(k)
         if self.wide_cap is not None:
             if self.wide_sticky is None or self.wide_sticky.device != k.device:
                 # (allocated by the first forward that runs with a capacity -- normally an eager warm-up; inside a capture the fill below
@@ -384,6 +399,24 @@ class ShardedDGGConv:
         if not chunked and self.wide_rows == "auto":
             return None
         return lay
+
+    def _chunk_layout_edge_list(self, k):
+        """_chunk_layout on edge-list candidates (wide_rows "auto" only; no fixed capacity, so not inside a capture): the layout of the
+        CLAMPED degrees min(k_i, n_i - 9.5) of the rank's rows -- row i gets the chunks of its min(n_i, ceil(k_i + 8.5) + 1) ranks that can
+        carry weight, so a row with 3 candidates and k = 1000 gets one chunk -- or None while every row fits the 64-rank list (the list
+        kernels then run, unchanged).  The kernels, the ramp and every backward keep the true k.  Each rank decides from its own rows:
+        edge lists always use the per-pair hash keyed on global ids, and no collective depends on the layout."""
+        if self.wide_rows != "auto" or self.wide_cap is not None or (k.is_cuda and torch.cuda.is_current_stream_capturing()):
+            return None
+        rowptr = self._cand_rows()[0]
+        ent = self._lens_cache                               # (n_i - 9.5 of the rank's rows, cached on the candidate slice's identity)
+        if ent is None or ent[0]() is not rowptr:
+            ent = self._lens_cache = (weakref.ref(rowptr), (rowptr[1:] - rowptr[:-1]).to(torch.float32) - 9.5)
+        lay = self.kern.chunk_layout(torch.minimum(k, ent[1]), ncols=self.N)
+        if lay is None:
+            return None
+        self.last_layout = (lay.chunks, lay.maxm)
+        return lay if lay.wide else None
 
     def _row_bound(self, xp, k):
         """-> lpub [own rows] or None.  The ranked search bounds the score of the ranks it has not reached by their noise alone, i.e. as
@@ -563,12 +596,17 @@ class ShardedDGGConv:
         return (idx, val) + tuple(kern.softk_fwd(idx, val, k, self.mode))
 
     def _search_edge_list(self, s, deg_full):
-        """_search on edge-list candidates (cand), u-v-dist or the edge-MLP scorer"""
+        """_search on edge-list candidates (cand), u-v-dist or the edge-MLP scorer, on the 64-rank list or on chunked rows.  Writes s:
+        layout, ncand and with a scorer AB, sdeg, ex (per candidate on the list, per kept slot -- flat -- on chunked rows), eid (None on
+        chunked rows, whose backward runs in CSR form on the flattened chunks)"""
         kern, xp, k = self.kern, s["xp"], s["k"]
         # a row shard: its rows' rebased CSR slice and the row-range entries (rows=); the whole graph: exactly the one-rank calls
         rowptr, col, (e0, e1) = self._cand_rows()
         rk = {} if (self.r0, self.r1) == (0, self.N) else {"rows": (self.r0, self.r1)}
         s["ncand"] = int(col.numel())
+        # rows wider than 64 ranks whose learned degrees need them (wide_rows "auto"): min(n_i, ceil(k_i + 8.5) + 1) ranks of every row in
+        # chunks of 64, the ramp fused into the search; None: every row fits the list, and the list kernels run as they always have
+        s["layout"] = lay = self._chunk_layout(k) if (xp.shape[1] in KERNEL_WIDTHS and self.mode in (0, 1)) else None
         if self.scorer is not None:
             # edge-MLP scorer: first layer split into per-node products AB = xp [Wa | Wb]^T (MFMA GEMM, all N nodes) + per-edge terms
             sc = self.scorer
@@ -579,8 +617,22 @@ class ShardedDGGConv:
             s["sdeg"] = sdeg = deg_full if sc["wdu"] is not None else None
             p_edge, s["ex"] = kern.edge_mlp_fwd(AB, xp, erow, col, sdeg, ex_in, sc["ex_mode"], sc["t_ex"], sc["wdu"], sc["wdv"],
                                                 sc["wex"], sc["b1"], sc["w2"], sc["b2"], sc["act"])
+            if lay is not None:
+                # (ex per kept slot, flat; no eid: the backward runs in CSR form on the flattened chunks, _scorer_backward_chunked)
+                got = kern.edgelist_topk_p_chunked(p_edge, self.N, rowptr, col, k, lay, self.mode, self.noise_mode, self.seed, ex_edge=s["ex"], **rk)
+                if got is None:
+                    raise NotImplementedError("ShardedDGGConv: the kernel namespace has no edgelist_topk_p_chunked (edge-list candidates, "
+                                              "edge-MLP scorer, chunked rows)")
+                idx, val, ex, w, rs_local = got
+                s["ex"], s["eid"] = (None if ex is None else ex.reshape(-1)), None
+                return idx, val, w, rs_local
             idx, val, s["eid"] = kern.edgelist_topk_p(p_edge, self.N, rowptr, col, self.K, self.noise_mode, None, self.seed, **rk)
             return (idx, val) + tuple(kern.softk_fwd(idx, val, k, self.mode))
+        if lay is not None:
+            got = kern.edgelist_topk_chunked(xp, rowptr, col, k, lay, self.mode, self.t, self.noise_mode, self.seed, **rk)
+            if got is None:
+                raise NotImplementedError("ShardedDGGConv: the kernel namespace has no edgelist_topk_chunked (edge-list candidates, chunked rows)")
+            return got
         got = kern.edgelist_topk_softk(xp, rowptr, col, k, self.mode, self.K, self.t, self.noise_mode, None, self.seed,
                                        overflow=self.overflow, **rk)
         if got is not None:                         # search + ramp in one launch
@@ -832,7 +884,8 @@ class ShardedDGGConv:
         return dxp, dk
 
     def _scorer_backward_chunked(self, g, dA, da, ahat_rows, kw):
-        """_scorer_backward on chunked rows (all-pairs candidates): ramp + normalisation backward by node over the row's chunks
+        """_scorer_backward on chunked rows (all-pairs or edge-list candidates: a chunked row does not say where it came from): ramp +
+        normalisation backward by node over the row's chunks
         (softk_bwd_rows_chunked; da = the neighbour-side sums), then the MLP's backward in its CSR form on the flattened chunks -- row i's
         entries are [64 cptr[i], 64 cptr[i+1]), empty slots carry idx = -1 and are skipped; parameter sums in a fixed order -- and the
         distance term of u-v-deg-dist through csr_uvdist_bwd on the same pattern.  kw: rows= of a row shard."""
