@@ -284,6 +284,13 @@ __device__ __forceinline__ void row16_first_impl(int v, int (&out)[N], std::inte
 template <int N>
 __device__ __forceinline__ void row16_first(int v, int (&out)[N]) { row16_first_impl<N>(v, out, std::make_integer_sequence<int, N>{}); }
 
+// one of them: v of lane U of the caller's 16-lane row
+template <int U>
+__device__ __forceinline__ int row16_lane(int v) {
+    static_assert(U >= 0 && U < 16, "row_share selects a lane of a 16-lane row");
+    return __builtin_amdgcn_update_dpp(0, v, 0x150 + U, 0xF, 0xF, false);
+}
+
 // lane ^ D exchange without the LDS crossbar: DPP quad_perm / row shifts / row_ror for D < 16,
 // v_permlane16_swap / v_permlane32_swap (gfx950) for D = 16 / 32.  ~1-3 VALU ops instead of a ds_bpermute round trip.
 template <int D>

@@ -204,6 +204,79 @@ struct SoftkArgs {
     const int *recpos;
     const float *dA_rec;
 };
+// The first NB batches (of NPI entries) of the group of entries that starts at rank r0: gathers, squared distances, the scalar chain
+// once per entry in the lane that owns it, accumulation -- see edge_bwd_rows.  NB is a template parameter so that every batch register
+// is named (a run-time bound inside the unrolled loops cost 30 registers, or scratch at H = 128).  -> dd of this lane's entry
+template <int H, int R0, int NB>
+__device__ __forceinline__ float edge_rows_group(const float *__restrict__ xp, int64_t gi, int K, int lane, int32_t jl, bool myact,
+                                                 bool mine, float gl, float vl, float t, int perturb, const float4 xi, float4 &acc) {
+    constexpr int LPR = H / 4, NPI = 64 / LPR, r0 = R0;
+    const int c4 = lane % LPR, slot = lane / LPR;
+    float4 xj[NB];
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const int r = r0 + b * NPI + slot;
+        const int rr = r < 64 ? r : 63;
+        const int32_t jb = __shfl(jl, rr, 64);
+        const bool ab = __shfl((int)myact, rr, 64) != 0 && r < K;
+        xj[b] = *reinterpret_cast<const float4 *>(xp + (ab ? (int64_t)jb : gi) * H + 4 * c4);
+    }
+    float myd2 = 0.0f;
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const float4 d = make_float4(xi.x - xj[b].x, xi.y - xj[b].y, xi.z - xj[b].z, xi.w - xj[b].w);   // 0 when inactive
+        float d2 = d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
+        if (LPR > 16) d2 += __uint_as_float(xor_shfl<16>(__float_as_uint(d2), lane));
+        if (LPR > 8) d2 += __uint_as_float(xor_shfl<8>(__float_as_uint(d2), lane));
+        if (LPR > 4) d2 += __uint_as_float(xor_shfl<4>(__float_as_uint(d2), lane));
+        if (LPR > 2) d2 += __uint_as_float(xor_shfl<2>(__float_as_uint(d2), lane));
+        d2 += __uint_as_float(xor_shfl<1>(__float_as_uint(d2), lane));
+        // entry r0 + b*NPI + s was reduced by slot s: its owner lane fetches it from that slot's first lane
+        const float tq = __shfl(d2, (lane % NPI) * LPR, 64);
+        if ((lane - r0) / NPI == b && mine) myd2 = tq;
+    }
+    float mydd = 0.0f;
+    if (mine && myact && myd2 != 0.0f) {                         // vector_norm backward at 0 is 0 (self loop)
+        const float dist = sqrtf(myd2);
+        const float p = c_exp(t * dist);
+        const float dp = perturb ? gl * vl / (p + 1e-8f) : gl;
+        mydd = dp * t * p / dist;
+    }
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const int r = r0 + b * NPI + slot;
+        const float dd = __shfl(mydd, r < 64 ? r : 63, 64);      // (outside any select: see conv_bwd_node)
+        const float4 d = make_float4(xi.x - xj[b].x, xi.y - xj[b].y, xi.z - xj[b].z, xi.w - xj[b].w);
+        acc.x += dd * d.x; acc.y += dd * d.y; acc.z += dd * d.z; acc.w += dd * d.w;
+    }
+    return mydd;
+}
+// wave-uniform choice of the body for nbat batches (1 <= nbat <= NBT), in steps of NBT / 8 batches where NBT > 8 (H = 128)
+template <int H, int R0, int NBT, int NB = NBT>
+__device__ __forceinline__ float edge_rows_pick(int nbat, const float *__restrict__ xp, int64_t gi, int K, int lane, int32_t jl,
+                                                bool myact, bool mine, float gl, float vl, float t, int perturb, const float4 xi, float4 &acc) {
+    constexpr int STEP = NBT > 8 ? NBT / 8 : 1;
+    if constexpr (NB > STEP) {
+        if (nbat <= NB - STEP) return edge_rows_pick<H, R0, NBT, NB - STEP>(nbat, xp, gi, K, lane, jl, myact, mine, gl, vl, t, perturb, xi, acc);
+    }
+    return edge_rows_group<H, R0, NB>(xp, gi, K, lane, jl, myact, mine, gl, vl, t, perturb, xi, acc);
+}
+
+// the group of 32 entries that starts at rank R0 (lane r owns entry r).  Only the batches up to the group's HIGHEST active lane are run
+// (wave-uniform count): a row has ~k + 9 = 41 live entries, so 5 of the second group's 8 batches (H = 64) held nothing.  A batch that is
+// left out added dd * (xi - xi) = +0 to acc and left myd2 / mydd of its lanes at 0: identical bits.  Holes below that lane stay masked.
+template <int H, bool COEF, int R0>
+__device__ __forceinline__ void edge_rows_half(const float *__restrict__ xp, int64_t gi, int K, int lane, int32_t jl, bool myact, float gl, float vl,
+                                               float t, int perturb, const float4 xi, float4 &acc, float &mycoef) {
+    constexpr int NPI = 64 / (H / 4), NBT = 32 / NPI;
+    const bool mine = lane >= R0 && lane < R0 + 32;
+    const unsigned long long actmask = __ballot(mine && myact);
+    if (actmask == 0ull) return;                                 // wave-uniform: no active entry in this group
+    const int nbat = (63 - __clzll(actmask) - R0) / NPI + 1;
+    const float mydd = edge_rows_pick<H, R0, NBT>(nbat, xp, gi, K, lane, jl, myact, mine, gl, vl, t, perturb, xi, acc);
+    if (COEF && mine) mycoef = mydd;
+}
+
 template <int H, bool FUSE, bool PAY = false>
 __global__ __launch_bounds__(256) void edge_bwd_rows(const float *__restrict__ xp, int64_t rows, const int32_t *__restrict__ idx,
                                                      const float *__restrict__ val, const float *__restrict__ dval, int K,
@@ -268,48 +341,9 @@ __global__ __launch_bounds__(256) void edge_bwd_rows(const float *__restrict__ x
     // Same operations per entry and the same accumulation order: identical bits.
     constexpr int NBT = (32 / NPI) < 1 ? 1 : 32 / NPI;           // 32 entries per iteration (two iterations for K = 64)
     const bool myact = lane < K && jl >= 0 && gl != 0.0f;
-    for (int r0 = 0; r0 < K; r0 += NBT * NPI) {
-        const bool mine = lane >= r0 && lane < r0 + NBT * NPI;
-        if (__ballot(mine && myact) == 0ull) continue;           // wave-uniform: no active entry in this group
-        float4 xj[NBT];
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
-            const int r = r0 + b * NPI + slot;
-            const int rr = r < 64 ? r : 63;
-            const int32_t jb = __shfl(jl, rr, 64);
-            const bool ab = __shfl((int)myact, rr, 64) != 0 && r < K;
-            xj[b] = *reinterpret_cast<const float4 *>(xp + (ab ? (int64_t)jb : gi) * H + 4 * c4);
-        }
-        float myd2 = 0.0f;
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
-            const float4 d = make_float4(xi.x - xj[b].x, xi.y - xj[b].y, xi.z - xj[b].z, xi.w - xj[b].w);   // 0 when inactive
-            float d2 = d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
-            if (LPR > 16) d2 += __uint_as_float(xor_shfl<16>(__float_as_uint(d2), lane));
-            if (LPR > 8) d2 += __uint_as_float(xor_shfl<8>(__float_as_uint(d2), lane));
-            if (LPR > 4) d2 += __uint_as_float(xor_shfl<4>(__float_as_uint(d2), lane));
-            if (LPR > 2) d2 += __uint_as_float(xor_shfl<2>(__float_as_uint(d2), lane));
-            d2 += __uint_as_float(xor_shfl<1>(__float_as_uint(d2), lane));
-            // entry r0 + b*NPI + s was reduced by slot s: its owner lane fetches it from that slot's first lane
-            const float tq = __shfl(d2, (lane % NPI) * LPR, 64);
-            if ((lane - r0) / NPI == b && mine) myd2 = tq;
-        }
-        float mydd = 0.0f;
-        if (mine && myact && myd2 != 0.0f) {                     // vector_norm backward at 0 is 0 (self loop)
-            const float dist = sqrtf(myd2);
-            const float p = c_exp(t * dist);
-            const float dp = perturb ? gl * vl / (p + 1e-8f) : gl;
-            mydd = dp * t * p / dist;
-        }
-        if (!PAY && mine) mycoef = mydd;                         // lane r owns entry r
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
-            const int r = r0 + b * NPI + slot;
-            const float dd = __shfl(mydd, r < 64 ? r : 63, 64);  // (outside any select: see conv_bwd_node)
-            const float4 d = make_float4(xi.x - xj[b].x, xi.y - xj[b].y, xi.z - xj[b].z, xi.w - xj[b].w);
-            acc.x += dd * d.x; acc.y += dd * d.y; acc.z += dd * d.z; acc.w += dd * d.w;
-        }
-    }
+    static_assert(NBT * NPI == 32, "two groups of 32 entries");
+    edge_rows_half<H, !PAY, 0>(xp, gi, K, lane, jl, myact, gl, vl, t, perturb, xi, acc, mycoef);
+    if (K > 32) edge_rows_half<H, !PAY, 32>(xp, gi, K, lane, jl, myact, gl, vl, t, perturb, xi, acc, mycoef);
     // sum the NPI neighbour slots (lanes with equal c4)
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1) {
@@ -691,49 +725,54 @@ __global__ __launch_bounds__(256) void conv_bwd_cols(const float *__restrict__ G
 constexpr int NODE_LONG = 128;
 constexpr int64_t NODE_SPLIT_MAX = 65536;
 
+// The walk of one wavefront over the records [pb, pe) of its node, WALK_BLOCK = 64 records at a time: ONE record load per block (lane l
+// takes one record), then only gathers.  (Before: a record load at the head of every NBT * NPI = 16 records, which the gathers of that
+// iteration waited for -- a node of ~41 records was a chain nodeptr -> recs -> G rows -> recs -> G rows -> recs -> G rows.)  The block's
+// batches of NPI records are gathered and consumed in groups of NBT = 4, and only the groups that hold a record are run (wave-uniform
+// count).  What is per RECORD and not per batch is done once per block by the lane that loaded the record: the dA_ext word is loaded
+// there (before: NBT four-address loads per group), and dA is stored from there with dA_rec (before: one four-lane store per batch).
+// Record n of a block is worked on in batch n / NPI by lane group n % NPI, batches ascending: the order every lane accumulated in
+// before, so dH_j, da_j and dA keep their bits for a given record order.
+constexpr int WALK_BLOCK = 64;
 template <int F, bool EXT>
-__device__ __forceinline__ void conv_bwd_walk(const float *__restrict__ G, int K, int pb, int pe, int p1, const int4 *__restrict__ recs,
-                                              const float4 hj, const float aj, float *__restrict__ dA, float *__restrict__ dA_rec,
-                                              const float *__restrict__ dA_ext, int lane, float4 &acc, float &sda, const int wide = 0) {
-    // (wide: chunked rows -- a record's first word is chunk * 64 + entry and its second word the SOURCE NODE of the chunk, see pp_sort)
-    constexpr int LPR = F / 4, NPI = 64 / LPR, NBT = 4, PER = NBT * NPI;          // PER records per iteration (<= 64)
-    const int c4 = lane % LPR, slot = lane / LPR;
-    // ROWSHARE (groups of 16 lanes = DPP rows, F = 64): record q = b * NPI + slot of an iteration is LOADED by lane 16 slot + b, a lane
-    // of the group that works on it in batch b -- its fields then reach the group by DPP row_share (one vector instruction each) instead
-    // of ds_bpermute through the LDS crossbar, and the reduced dot product is already in the lane that stores it (203 -> 199 us at
-    // N = 100k; the same change in edge_bwd_walk measured nothing and was not kept)
-    constexpr bool ROWSHARE = LPR == 16;
-    for (int e0 = pb; e0 < pe; e0 += PER) {
-        // lane l: record e0 + l (ROWSHARE: e0 + (l % 16) * NPI + l / 16; unconditional, clamped load; a lane past the range marks its copy invalid)
-        const int myq = ROWSHARE ? c4 * NPI + slot : lane;
-        const bool have = (ROWSHARE ? c4 < NBT : lane < PER) && e0 + myq < pe;
-        int4 myrec = recs[have ? e0 + myq : p1 - 1];
-        if (!have) myrec.y = -1;
-        int src[NBT];
-        float cf[NBT];
-        float4 g[NBT];
-        int bx[NBT], by[NBT], bz[NBT];
-        if constexpr (ROWSHARE) { dgg::row16_first<NBT>(myrec.x, bx); dgg::row16_first<NBT>(myrec.y, by); dgg::row16_first<NBT>(myrec.z, bz); }
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
-            const int q = b * NPI + slot;                        // record of this lane's group in batch b
-            src[b] = ROWSHARE ? bx[b] : __shfl(myrec.x, q, 64);
-            const int dst = ROWSHARE ? by[b] : __shfl(myrec.y, q, 64);
+struct ConvWalk {
+    static constexpr int LPR = F / 4, NPI = 64 / LPR, NBT = 4, PER = NBT * NPI, NG = WALK_BLOCK / PER;
+    // ROWSHARE (groups of 16 lanes = DPP rows, F = 64): record n = B * NPI + slot of a block is LOADED by lane 16 slot + B, a lane of the
+    // group that works on it in batch B -- its fields then reach the group by DPP row_share (one vector instruction each) instead of
+    // ds_bpermute through the LDS crossbar, and the reduced dot product is already in the lane that stores it
+    static constexpr bool ROWSHARE = LPR == 16;
+    const float *__restrict__ G;
+    float4 hj;
+    float aj;
+    int lane, c4, slot, wide;
+    int4 myrec;                                                  // this lane's record of the block (y = -1: none)
+    float myext;                                                 // EXT: its dA_ext word (0: none)
+
+    // v of the lane that loaded the record of batch B of this lane's group
+    // (ROWSHARE: the batch is a compile-time number, boff = 0; else batch B + boff with boff a wave-uniform variable)
+    template <int B>
+    __device__ __forceinline__ int field(int v, int boff) const {
+        if constexpr (ROWSHARE) return dgg::row16_lane<B>(v);
+        else return __shfl(v, (B + boff) * NPI + slot, 64);
+    }
+    template <int GI, int b = 0>
+    __device__ __forceinline__ void gather(int boff, float4 (&g)[NBT], float (&cf)[NBT]) const {
+        if constexpr (b < NBT) {
+            constexpr int B = GI * NBT + b;
+            const int src = field<B>(myrec.x, boff);
+            const int dst = field<B>(myrec.y, boff);
             // (every shuffle OUTSIDE the select: `c ? shfl : 0` would run the shuffle under a divergent mask, and a lane that is
             // masked off there hands 0 to the lanes that read from it)
-            const float wa = __int_as_float(ROWSHARE ? bz[b] : __shfl(myrec.z, q, 64));
+            const float wa = __int_as_float(field<B>(myrec.z, boff));
             cf[b] = dst >= 0 ? __fmul_rn(wa, aj) : 0.0f;
-            if (dst < 0) src[b] = -1;
-            g[b] = *reinterpret_cast<const float4 *>(G + (int64_t)(src[b] < 0 ? 0 : (wide ? dst : (src[b] >> 6))) * F + 4 * c4);   // unconditional
+            g[b] = *reinterpret_cast<const float4 *>(G + (int64_t)(dst < 0 ? 0 : (wide ? dst : (src >> 6))) * F + 4 * c4);   // unconditional
+            gather<GI, b + 1>(boff, g, cf);
         }
-        float ext[NBT];
-        if constexpr (EXT) {
-#pragma unroll
-            for (int b = 0; b < NBT; b++) ext[b] = src[b] >= 0 ? dA_ext[(int64_t)(src[b] >> 6) * K + (src[b] & 63)] : 0.0f;
-        }
-        float mydot = 0.0f;
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
+    }
+    template <int GI, int b = 0>
+    __device__ __forceinline__ void consume(int boff, const float4 (&g)[NBT], const float (&cf)[NBT], float &mydot, float4 &acc, float &sda) const {
+        if constexpr (b < NBT) {
+            constexpr int B = GI * NBT + b;
             float dot = g[b].x * hj.x;
             dot = fmaf(g[b].y, hj.y, dot); dot = fmaf(g[b].z, hj.z, dot); dot = fmaf(g[b].w, hj.w, dot);
             if (LPR > 16) dot += __uint_as_float(xor_shfl<16>(__float_as_uint(dot), lane));
@@ -741,23 +780,70 @@ __device__ __forceinline__ void conv_bwd_walk(const float *__restrict__ G, int K
             if (LPR > 4) dot += __uint_as_float(xor_shfl<4>(__float_as_uint(dot), lane));
             dot += __uint_as_float(xor_shfl<2>(__float_as_uint(dot), lane));
             dot += __uint_as_float(xor_shfl<1>(__float_as_uint(dot), lane));
-            if constexpr (EXT) dot += ext[b];
-            // (write-through store that does not stay in the XCD's L2: these 4.1 M scattered dwords are never touched again by this
-            //  kernel, and left in L2 they push out the G rows the gathers hit: 202 -> 193 us; nontemporal: 196)
-            if (dA && src[b] >= 0 && c4 == 0)                    // (dA == NULL: the row kernel reads dA_rec through the slot -> record map)
-                __hip_atomic_store(&dA[(int64_t)(src[b] >> 6) * K + (src[b] & 63)], dot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // back to the lane that loaded the record: record order, one store per iteration
+            if constexpr (EXT) dot += __int_as_float(field<B>(__float_as_int(myext), boff));
+            // back to the lane that loaded the record: record order, one store per block
             if constexpr (ROWSHARE) {
-                if (c4 == b) mydot = dot;                        // (every lane of the group holds the reduced value)
+                if (c4 == B) mydot = dot;                        // (every lane of the group holds the reduced value)
             } else {
                 const float tq = __shfl(dot, (lane % NPI) * LPR, 64);
-                if (lane / NPI == b) mydot = tq;
+                if (lane / NPI == B + boff) mydot = tq;
             }
             acc.x = fmaf(cf[b], g[b].x, acc.x); acc.y = fmaf(cf[b], g[b].y, acc.y);
             acc.z = fmaf(cf[b], g[b].z, acc.z); acc.w = fmaf(cf[b], g[b].w, acc.w);
             sda = fmaf(dot, cf[b], sda);
+            consume<GI, b + 1>(boff, g, cf, mydot, acc, sda);
         }
-        if (have) dA_rec[e0 + myq] = mydot;
+    }
+    // groups GI, GI + 1, ... of a block of nrec records (wave-uniform)
+    template <int GI = 0>
+    __device__ __forceinline__ void groups(int nrec, float &mydot, float4 &acc, float &sda) const {
+        if constexpr (ROWSHARE) {
+            float4 g[NBT];
+            float cf[NBT];
+            gather<GI>(0, g, cf);
+            consume<GI>(0, g, cf, mydot, acc, sda);
+            if constexpr (GI + 1 < NG) {
+                if (nrec > (GI + 1) * PER) groups<GI + 1>(nrec, mydot, acc, sda);
+            }
+        } else {
+            for (int gi = 0; gi * PER < nrec; gi++) {
+                float4 g[NBT];
+                float cf[NBT];
+                gather<0>(gi * NBT, g, cf);
+                consume<0>(gi * NBT, g, cf, mydot, acc, sda);
+            }
+        }
+    }
+};
+
+template <int F, bool EXT>
+__device__ __forceinline__ void conv_bwd_walk(const float *__restrict__ G, int K, int pb, int pe, int p1, const int4 *__restrict__ recs,
+                                              const float4 hj, const float aj, float *__restrict__ dA, float *__restrict__ dA_rec,
+                                              const float *__restrict__ dA_ext, int lane, float4 &acc, float &sda, const int wide = 0) {
+    // (wide: chunked rows -- a record's first word is chunk * 64 + entry and its second word the SOURCE NODE of the chunk, see pp_sort)
+    using W = ConvWalk<F, EXT>;
+    constexpr int LPR = W::LPR, NPI = W::NPI;
+    W wk{G, hj, aj, lane, lane % LPR, lane / LPR, wide, make_int4(0, 0, 0, 0), 0.0f};
+    // lane l: record e0 + l (ROWSHARE: e0 + (l % 16) * NPI + l / 16)
+    const int myq = W::ROWSHARE ? wk.c4 * NPI + wk.slot : lane;
+    for (int e0 = pb; e0 < pe; e0 += WALK_BLOCK) {               // (no read for an empty range: p1 - 1 may be -1)
+        const int nrec = pe - e0 < WALK_BLOCK ? pe - e0 : WALK_BLOCK;
+        const bool have = myq < nrec;
+        wk.myrec = recs[have ? e0 + myq : p1 - 1];               // unconditional, clamped load; a lane past the range marks its copy invalid
+        const int64_t myslot = (int64_t)(wk.myrec.x >> 6) * K + (wk.myrec.x & 63);
+        if (!have) wk.myrec.y = -1;
+        if constexpr (EXT) {
+            const float e = dA_ext[myslot];                      // (unconditional: a lane past the range reads the word of the node's last record)
+            wk.myext = have ? e : 0.0f;
+        }
+        float mydot = 0.0f;
+        wk.groups(nrec, mydot, acc, sda);
+        if (have) {
+            dA_rec[e0 + myq] = mydot;
+            // (write-through store that does not stay in the XCD's L2: these 4.1 M scattered dwords are never touched again by this
+            //  kernel, and left in L2 they push out the G rows the gathers hit: 202 -> 193 us; nontemporal: 196)
+            if (dA) __hip_atomic_store(&dA[myslot], mydot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (dA == NULL: read through the slot -> record map)
+        }
     }
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1) {
@@ -773,7 +859,7 @@ __global__ __launch_bounds__(256) void conv_bwd_node(const float *__restrict__ G
                                                      const float *__restrict__ rs, float *__restrict__ dA, float *__restrict__ dA_rec,
                                                      float *__restrict__ dH, float *__restrict__ da, const float *__restrict__ dA_ext = nullptr,
                                                      unsigned nmain = 0, int wide = 0) {
-    constexpr int LPR = F / 4, PER = 4 * (64 / LPR);
+    constexpr int LPR = F / 4, PER = WALK_BLOCK;                  // (a long node's quarters are cut at whole blocks of the walk)
     __shared__ float4 part[4][LPR];
     __shared__ float parts[4];
     const int lane = threadIdx.x & 63, c4 = lane % LPR, slot = lane / LPR, wave = dgg::wave_id();
@@ -819,16 +905,80 @@ __global__ __launch_bounds__(256) void conv_bwd_node(const float *__restrict__ G
 // loaded a record forms d loss / d score for it (PER records in parallel), the distance part runs per lane group.
 // dxp_j is the exclusive property of this wavefront: rows inside [row0, row0 + rows) already hold the row-side term written by
 // edge_bwd_rows (read-modify-write), the others are written plainly (no zero fill needed).
+// The first NB batches (of NPI records) of the group of records that lane r0 .. r0 + NBT * NPI - 1 of the wavefront loaded: unconditional
+// gathers (an inactive slot re-reads xp_j, whose distance to itself is 0: dd = 0), squared distances, each handed to the lane that
+// loaded the record; the scalar chain (sqrt, exp, two divisions) then runs ONCE per record instead of on all H/4 lanes of every batch
+// (the kernel was VALU-bound: 515 VALU per 16 records); accumulation.  NB is a template parameter: named batch registers.
+template <int H, int R0, int NB>
+__device__ __forceinline__ void edge_walk_group(const float *__restrict__ xp, int64_t j, const int4 myrec, const float mydval,
+                                                const float4 xj, int64_t row0, float t, int perturb, int lane, int wide, float4 &acc) {
+    constexpr int LPR = H / 4, NPI = 64 / LPR, NBT = (32 / NPI) < 1 ? 1 : 32 / NPI;
+    const int c4 = lane % LPR, slot = lane / LPR;
+    constexpr int r0 = R0;
+    const bool mine = lane >= r0 && lane < r0 + NBT * NPI;
+    float4 xi[NB];
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const int q = r0 + b * NPI + slot;
+        const int src = __shfl(myrec.x, q, 64);                  // every shuffle outside a select (see conv_bwd_node)
+        const int dst = __shfl(myrec.y, q, 64);
+        xi[b] = *reinterpret_cast<const float4 *>(xp + (dst >= 0 ? row0 + (wide ? dst : (src >> 6)) : j) * H + 4 * c4);
+    }
+    float myd2 = 0.0f;
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const float4 d = make_float4(xi[b].x - xj.x, xi[b].y - xj.y, xi[b].z - xj.z, xi[b].w - xj.w);
+        float d2 = d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
+        if (LPR > 16) d2 += __uint_as_float(xor_shfl<16>(__float_as_uint(d2), lane));
+        if (LPR > 8) d2 += __uint_as_float(xor_shfl<8>(__float_as_uint(d2), lane));
+        if (LPR > 4) d2 += __uint_as_float(xor_shfl<4>(__float_as_uint(d2), lane));
+        d2 += __uint_as_float(xor_shfl<2>(__float_as_uint(d2), lane));
+        d2 += __uint_as_float(xor_shfl<1>(__float_as_uint(d2), lane));
+        const float tq = __shfl(d2, (lane % NPI) * LPR, 64);
+        if ((lane - r0) / NPI == b && mine) myd2 = tq;
+    }
+    float mydd = 0.0f;
+    if (mine && mydval != 0.0f && myd2 != 0.0f) {                // vector_norm backward at 0 is 0 (self loop)
+        const float dist = sqrtf(myd2);
+        const float p = c_exp(t * dist);
+        const float dp = perturb ? mydval * __int_as_float(myrec.w) / (p + 1e-8f) : mydval;
+        mydd = dp * t * p / dist;
+    }
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const float dd = __shfl(mydd, r0 + b * NPI + slot, 64);
+        const float4 d = make_float4(xi[b].x - xj.x, xi[b].y - xj.y, xi[b].z - xj.z, xi[b].w - xj.w);
+        acc.x -= dd * d.x; acc.y -= dd * d.y; acc.z -= dd * d.z; acc.w -= dd * d.w;
+    }
+}
+// wave-uniform choice of the body for nbat batches (1 <= nbat <= NBT), in steps of NBT / 8 batches where NBT > 8 (H = 128)
+template <int H, int R0, int NBT, int NB = NBT>
+__device__ __forceinline__ void edge_walk_pick(int nbat, const float *__restrict__ xp, int64_t j, const int4 myrec, const float mydval,
+                                               const float4 xj, int64_t row0, float t, int perturb, int lane, int wide, float4 &acc) {
+    constexpr int STEP = NBT > 8 ? NBT / 8 : 1;
+    if constexpr (NB > STEP) {
+        if (nbat <= NB - STEP) return edge_walk_pick<H, R0, NBT, NB - STEP>(nbat, xp, j, myrec, mydval, xj, row0, t, perturb, lane, wide, acc);
+    }
+    edge_walk_group<H, R0, NB>(xp, j, myrec, mydval, xj, row0, t, perturb, lane, wide, acc);
+}
+
+// The walk of one wavefront over the records [pb, pe) of its node, WALK_BLOCK = 64 records at a time.  ONE load of the records and of
+// dA_rec and one rowinfo gather per block, d loss / d score (the tanh chain) formed once on all 64 lanes -- before: every 32 records,
+// on half the lanes, at the head of the gathers that then waited for it.  The block's records are worked on in two groups of
+// NBT * NPI = 32 (lanes 0..31, 32..63), and of each group only the batches that hold a record (wave-uniform count, from pe - e0): a node
+// has ~41 records, so 5 of the second group's 8 batches (H = 64) held nothing.  A batch that is left out added dd * (xp_j - xp_j) = 0:
+// the sums keep their bits for a given record order.
 template <int H>
 __device__ __forceinline__ void edge_bwd_walk(const float *__restrict__ xp, int64_t j, int pb, int pe, int p1, const int4 *__restrict__ recs,
                                               const float *__restrict__ dA_rec, const float4 *__restrict__ rowinfo, const float4 xj, const float aj,
                                               int64_t row0, float t, int perturb, int lane, float4 &acc, const int wide = 0) {
     // (wide: chunked rows -- rowinfo is per CHUNK with the degree shifted by the chunk's first rank, k_i - 64 m, so that the entry's
     //  index inside its chunk still gives rank - k; the record's second word is the source node of the chunk, see pp_sort)
-    constexpr int LPR = H / 4, NPI = 64 / LPR, NBT = (32 / NPI) < 1 ? 1 : 32 / NPI, PER = NBT * NPI;   // 32 records per iteration
-    const int c4 = lane % LPR, slot = lane / LPR;
-    for (int e0 = pb; e0 < pe; e0 += PER) {
-        const bool have = lane < PER && e0 + lane < pe;
+    constexpr int LPR = H / 4, NPI = 64 / LPR, NBT = (32 / NPI) < 1 ? 1 : 32 / NPI, PER = NBT * NPI;   // 32 records per group
+    static_assert(2 * PER == WALK_BLOCK, "two groups per block");
+    for (int e0 = pb; e0 < pe; e0 += WALK_BLOCK) {               // (no read for an empty range: p1 - 1 may be -1)
+        const int nrec = pe - e0 < WALK_BLOCK ? pe - e0 : WALK_BLOCK;
+        const bool have = lane < nrec;
         const int ec = have ? e0 + lane : p1 - 1;                // unconditional, clamped loads
         int4 myrec = recs[ec];
         if (!have) myrec.y = -1;
@@ -839,43 +989,9 @@ __device__ __forceinline__ void edge_bwd_walk(const float *__restrict__ xp, int6
             const float th = c_tanh((float)(myrec.x & 63) - info.z);
             mydval = have ? dw * (1.0f - 0.5f * (1.0f + th)) : 0.0f;
         }
-        float4 xi[NBT];
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
-            const int q = b * NPI + slot;
-            const int src = __shfl(myrec.x, q, 64);             // every shuffle outside a select (see conv_bwd_node)
-            const int dst = __shfl(myrec.y, q, 64);
-            // unconditional gather; an inactive slot re-reads xp_j, whose distance to itself is 0 (dd = 0)
-            xi[b] = *reinterpret_cast<const float4 *>(xp + (dst >= 0 ? row0 + (wide ? dst : (src >> 6)) : j) * H + 4 * c4);
-        }
-        // squared distances, each handed to the lane that loaded the record; the scalar chain (sqrt, exp, two divisions) then runs
-        // ONCE per record instead of on all H/4 lanes of every batch (the kernel was VALU-bound: 515 VALU per 16 records)
-        float myd2 = 0.0f;
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
-            const float4 d = make_float4(xi[b].x - xj.x, xi[b].y - xj.y, xi[b].z - xj.z, xi[b].w - xj.w);
-            float d2 = d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
-            if (LPR > 16) d2 += __uint_as_float(xor_shfl<16>(__float_as_uint(d2), lane));
-            if (LPR > 8) d2 += __uint_as_float(xor_shfl<8>(__float_as_uint(d2), lane));
-            if (LPR > 4) d2 += __uint_as_float(xor_shfl<4>(__float_as_uint(d2), lane));
-            d2 += __uint_as_float(xor_shfl<2>(__float_as_uint(d2), lane));
-            d2 += __uint_as_float(xor_shfl<1>(__float_as_uint(d2), lane));
-            const float tq = __shfl(d2, (lane % NPI) * LPR, 64);
-            if (lane / NPI == b) myd2 = tq;
-        }
-        float mydd = 0.0f;
-        if (mydval != 0.0f && myd2 != 0.0f) {                    // vector_norm backward at 0 is 0 (self loop)
-            const float dist = sqrtf(myd2);
-            const float p = c_exp(t * dist);
-            const float dp = perturb ? mydval * __int_as_float(myrec.w) / (p + 1e-8f) : mydval;
-            mydd = dp * t * p / dist;
-        }
-#pragma unroll
-        for (int b = 0; b < NBT; b++) {
-            const float dd = __shfl(mydd, b * NPI + slot, 64);
-            const float4 d = make_float4(xi[b].x - xj.x, xi[b].y - xj.y, xi[b].z - xj.z, xi[b].w - xj.w);
-            acc.x -= dd * d.x; acc.y -= dd * d.y; acc.z -= dd * d.z; acc.w -= dd * d.w;
-        }
+        const int n0 = nrec < PER ? nrec : PER;
+        edge_walk_pick<H, 0, NBT>((n0 + NPI - 1) / NPI, xp, j, myrec, mydval, xj, row0, t, perturb, lane, wide, acc);
+        if (nrec > PER) edge_walk_pick<H, PER, NBT>((nrec - PER + NPI - 1) / NPI, xp, j, myrec, mydval, xj, row0, t, perturb, lane, wide, acc);
     }
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1) {
@@ -891,7 +1007,7 @@ __global__ __launch_bounds__(256) void edge_bwd_node(const float *__restrict__ x
                                                      const float4 *__restrict__ rowinfo, const float *__restrict__ rs, int normalized,
                                                      int64_t row0, int64_t rows, float t, int perturb, float *__restrict__ dxp, int out_act,
                                                      unsigned nmain = 0, int wide = 0) {
-    constexpr int LPR = H / 4, NPI = 64 / LPR, NBT = (32 / NPI) < 1 ? 1 : 32 / NPI, PER = NBT * NPI;
+    constexpr int LPR = H / 4, PER = WALK_BLOCK;                  // (a long node's quarters are cut at whole blocks of the walk)
     __shared__ float4 part[4][LPR];
     const int lane = threadIdx.x & 63, c4 = lane % LPR, slot = lane / LPR, wave = dgg::wave_id();
     const bool longmode = nmain != 0 && blockIdx.x >= nmain;      // (block-uniform)
