@@ -50,6 +50,42 @@ int dgg_edgelist_topk_p_chunked(const float *p_edge, int64_t N, int64_t row0, in
                                 int64_t ccap, const float *ex_edge, int32_t *idx, float *val, float *ex_out, int32_t *eid, float *w,
                                 float *rs, void *stream);
 
+/* ==== block norm_spmm ==== (dgg_amd._lib.NEXT_BLOCKS["norm_spmm"]; the declarations above are NEXT_PROTOTYPES) */
+
+/* ---- normalize_adj inside the forward aggregation ----------------------------------------------------------------------------------
+ * dgg_partp_build_phase / dgg_partp_build_chunked take three more values of `phase` (no prototype changes; phases 0..2 are as recorded,
+ * rs_all and ahat going together).  Phases 4 / 5 = phases 1 / 0 called with rs_all != NULL and ahat == NULL (required): the count pass
+ * still leaves ainv [ncols] = rs_all_j^-1/2 in the workspace, the fill pass writes the records only (no a_j gathers, no ahat stores);
+ * phase 2 finishes a phase 4.  Phase 3 runs the count pass alone (rs_all required; val / rs_rows / cnode are not read): the ainv table
+ * is complete, nothing else of the workspace is -- what a forward without a backward needs.
+ *
+ * Y [rows,F] = act(A H) AND ahat [rows,64] = rs_i^-1/2 w rs_j^-1/2 from the unnormalised weights: idx / w [rows,64] (K = 64), rs_rows
+ * [rows] the own rows' sums, partp_ws a payload workspace of (rows, 64, ncols) whose count pass ran with rs_all (its ainv table is
+ * read; no other part of it), X [ncols,F], F in {16, 32, 64}, X / Y 16-byte aligned.  ahat has the bits of dgg_partp_build_norm
+ * (a_i = 1 / sqrt(rs_i), (a_i * w) * ainv_j, 0 where idx < 0 or w == 0), Y the bits of dgg_ell_spmm_act_fwd on that ahat for finite X.
+ * act 0 / 2 as dgg_ell_spmm_act_fwd.  DGG_ERR_UNSUPPORTED: another F or alignment, no payload partition for the shape; DGG_ERR_ARG: a
+ * NULL array, act outside {0, 2}.  rows == 0 returns 0 without a launch. */
+int dgg_ell_spmm_norm_act_fwd(const int32_t *idx, const float *w, const float *rs_rows, const void *partp_ws, int64_t ncols, const float *X,
+                              int64_t rows, int F, int act, float *Y, float *ahat, void *stream);
+/* The same on chunked rows: idx / w / ahat [chunks,64], node i = the chunks [cptr[i], cptr[i+1]), rs_nodes [rows], partp_ws a workspace
+ * of (chunks, 64, ncols) (dgg_partp_build_chunked), Y [rows,F].  Chunks in [cptr[rows], chunks) get ahat = 0. */
+int dgg_ell_spmm_norm_act_fwd_chunked(const int32_t *idx, const float *w, const float *rs_nodes, const void *partp_ws, int64_t ncols,
+                                      const float *X, int64_t rows, const int32_t *cptr, int64_t chunks, int F, int act, float *Y,
+                                      float *ahat, void *stream);
+
+/* dgg_softk_edge_bwd_partp_phase / dgg_softk_edge_bwd_partp_chunked with ainv_table: 1 = the row kernel takes a_j = rs_j^-1/2 from the
+ * partition's ainv table (the partition was built with rs_all = rs: the same bits) instead of a division and a square root per lane;
+ * 0 = those entries.  Every other argument, refusal and result as theirs. */
+int dgg_softk_edge_bwd_partp_tab(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
+                                 const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
+                                 int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
+                                 float *dxp, int out_act, int phase, int ainv_table, void *stream);
+int dgg_softk_edge_bwd_partp_chunked_tab(const float *xp, int64_t rows, const int32_t *cptr, int64_t chunks, int h, const int32_t *idx,
+                                         const float *val, const float *k, const float *rs, const float *dA, const float *dA_rec,
+                                         const float *da, const float *ahat_rows, int64_t row0, float t, int perturb, int mode,
+                                         int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk, float *dxp,
+                                         int out_act, int phase, int ainv_table, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """ctypes binding of libdgg_hip.so.  The prototypes are not written here: PROTOTYPES / RESTYPES are parsed from the public header
 include/dgg_hip.h, the one description of the C ABI (the library's definitions are compiled against the same file).  Entry points added
 since that ABI version was recorded are declared in include/dgg_hip_next.h (purely additive, folded into dgg_hip.h at the next ABI bump)
-and parsed into tables of their own, NEXT_PROTOTYPES / NEXT_RESTYPES: PROTOTYPES stays the recorded ABI.  Fails loudly when the HIP
+and parsed into tables of their own, NEXT_PROTOTYPES / NEXT_RESTYPES (the header's first block) and NEXT_BLOCKS (one table per later
+block, by the name on its `==== block NAME ====` line): PROTOTYPES stays the recorded ABI.  Fails loudly when the HIP
 library or a header is missing: there is no CPU fallback anywhere in this package."""
 import ctypes as C
 import os
@@ -58,11 +59,26 @@ def _read_header(path=HEADER):
 _DECLS = _read_header()
 PROTOTYPES = {name: argtypes for name, (_, argtypes) in _DECLS.items() if name not in _INFO}    # name -> argtypes
 RESTYPES = {name: restype for name, (restype, _) in _DECLS.items() if name not in _INFO}        # name -> restype
-_NEXT_DECLS = _read_header(NEXT_HEADER)
+
+
+def _read_next_header(path=NEXT_HEADER):
+    """dgg_hip_next.h grows one BLOCK of declarations per change, each opened by a line `/* ==== block NAME ==== ... */` (the first block,
+    the chunked edge lists, has no such line) -> (declarations of the first block, {NAME: declarations})."""
+    if not os.path.exists(path):
+        raise DggHipError(f"{path} is missing: the ctypes prototypes are read from the public header")
+    with open(path) as f:
+        parts = re.split(r"^/\* ==== block (\w+) ====", f.read(), flags=re.M)
+    first = parse_header(parts[0], path)
+    return first, {name: parse_header("/* " + body, path) for name, body in zip(parts[1::2], parts[2::2])}
+
+
+_NEXT_DECLS, NEXT_BLOCKS = _read_next_header()
 NEXT_PROTOTYPES = {name: argtypes for name, (_, argtypes) in _NEXT_DECLS.items()}               # the same two tables for the entry
-NEXT_RESTYPES = {name: restype for name, (restype, _) in _NEXT_DECLS.items()}                   # points of dgg_hip_next.h
-if set(_NEXT_DECLS) & set(_DECLS):
-    raise DggHipError(f"{NEXT_HEADER} declares again what {HEADER} declares: {sorted(set(_NEXT_DECLS) & set(_DECLS))}")
+NEXT_RESTYPES = {name: restype for name, (restype, _) in _NEXT_DECLS.items()}                   # points of dgg_hip_next.h's first block
+_LATER_DECLS = {name: d for block in NEXT_BLOCKS.values() for name, d in block.items()}          # ... and of its later blocks, one table
+if set(_NEXT_DECLS) & set(_DECLS) or set(_LATER_DECLS) & (set(_DECLS) | set(_NEXT_DECLS)):
+    raise DggHipError(f"{NEXT_HEADER} declares again what {HEADER} or an earlier block of its own declares: "
+                      f"{sorted((set(_NEXT_DECLS) | set(_LATER_DECLS)) & set(_DECLS) | set(_LATER_DECLS) & set(_NEXT_DECLS))}")
 
 _lib = None
 
@@ -70,7 +86,7 @@ _lib = None
 def bind(L, names=None):
     """Gives the entry points `names` (default: every declared one, of both headers) of the CDLL handle L the headers' argtypes and
     restype."""
-    decls = {**_DECLS, **_NEXT_DECLS}
+    decls = {**_DECLS, **_NEXT_DECLS, **_LATER_DECLS}
     for name in (decls if names is None else names):
         fn = getattr(L, name)      # AttributeError if the library does not export a declared symbol
         fn.restype, fn.argtypes = decls[name]

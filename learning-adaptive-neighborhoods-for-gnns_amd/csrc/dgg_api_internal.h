@@ -45,6 +45,8 @@ int dgg_norm_da_cols_impl(const void *part_ws, int64_t rows, int K, int64_t ncol
 // payload partition (dgg_scatter.hip): nodeptr [ncols + 1] and the entry -> record map recpos [rows * 64] inside a built workspace
 // (0 on success; recpos is there only when dgg_partp_has_map(rows))
 int dgg_partp_internal_ptrs(const void *partp_ws, int64_t rows, int K, int64_t ncols, const int **nodeptr, const int **recpos);
+// ... and its table ainv [ncols] = rs_j^-1/2, complete once the count pass has run with rs_all (NULL: no payload partition for the shape)
+const float *dgg_partp_ainv(const void *partp_ws, int64_t rows, int K, int64_t ncols);
 int dgg_klimit_truncate_impl(const float *klim, int64_t rows, int K, int32_t *idx, float *val, hipStream_t st);
 
 // unperturbed chunked rows, front end (dgg_topk_sweep.hip): radius per row from a sampled sweep, one full fp16-MFMA sweep; the columns

@@ -9,6 +9,7 @@
 // reductions are 64-lane butterflies.
 #include "dgg_common.h"
 #include "dgg_api_internal.h"
+#include "../../include/dgg_hip_next.h"
 
 using namespace dgg;
 
@@ -262,19 +263,38 @@ __global__ void sddmm_slices_sum(const float *__restrict__ part, int64_t n, int 
 // of a feature are combined by an xor butterfly at the end (order: entry r goes to slot r mod (256/F), slots summed pairwise).
 // ACT 2 applies the ReLU of GCNConv (model.py:598) in the epilogue.
 // CHUNKED (rows wider than 64 ranks, K = 64): row i is the chunks [cptr[i], cptr[i+1]) of idx / ahat, walked in rank order.
-template <int F, bool CHUNKED = false>
+// NORM (K = 64): normalize_adj inside the aggregation.  `ahat` is the UNNORMALISED weight w, rs_rows the own rows' sums (per node on
+// chunked rows) and ainv [ncols] = rs_j^-1/2 the table the payload partition's count pass left: a = (a_i w) ainv_j, the expressions of
+// pp_fill (dgg_scatter.hip), is formed here and leaves as ahat_out -- one 64-lane store per row or chunk.  The F/4 lanes of a neighbour
+// read the same ainv_j beside their row gather (both addresses come from the shuffled index alone); of a slot's lanes, lane c4 keeps the
+// value of the row's batch c4 (64 / NPI = F/4 batches per row), i.e. of entry c4 * NPI + slot: no shuffle beyond the two per batch.
+// An entry counts iff idx >= 0 and w != 0 (pp_fill's rule); one whose product underflows to 0 adds fmaf(0, x, acc): Y as from ahat.
+template <int F, bool CHUNKED = false, bool NORM = false>
 __global__ __launch_bounds__(WPB * 64) void spmm_fwd_narrow(const int32_t *__restrict__ idx, const float *__restrict__ ahat,
                                                            const float *__restrict__ X, int64_t N, int K, int act,
-                                                           float *__restrict__ Y, const int32_t *__restrict__ cptr = nullptr) {
+                                                           float *__restrict__ Y, const int32_t *__restrict__ cptr = nullptr,
+                                                           const float *__restrict__ rs_rows = nullptr, const float *__restrict__ ainv = nullptr,
+                                                           float *__restrict__ ahat_out = nullptr, int64_t chunks = 0) {
     constexpr int LPR = F / 4, NPI = 64 / LPR, NBT = 4;
     const int lane = threadIdx.x & 63, c4 = lane % LPR, slot = lane / LPR;
     const int64_t i = (int64_t)blockIdx.x * WPB + dgg::wave_id();
     if (i >= N) return;
     const int64_t cb = CHUNKED ? (int64_t)cptr[i] : i, ce = CHUNKED ? (int64_t)cptr[i + 1] : i + 1;
+    float ai = 0.0f;
+    if constexpr (NORM) {
+        ai = inv_sqrt_c(rs_rows[i]);
+        if constexpr (CHUNKED)                                   // chunks past the last node's (spare capacity): empty, ahat = 0
+            for (int64_t ch = (int64_t)cptr[N] + i; ch < chunks; ch += N) ahat_out[ch * 64 + lane] = 0.0f;
+    }
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (int64_t ch = cb; ch < ce; ch++) {
-    const int32_t jl = lane < K ? idx[ch * K + lane] : -1;
-    const float al = lane < K ? ahat[ch * K + lane] : 0.0f;
+    int32_t jl = lane < K ? idx[ch * K + lane] : -1;
+    float al = lane < K ? ahat[ch * K + lane] : 0.0f;
+    float mine = 0.0f;
+    if constexpr (NORM) {
+        if (al == 0.0f) jl = -1;                                 // w == 0: outside the partition, ahat = 0
+        al = __fmul_rn(ai, al);                                  // wa = a_i * w, once per entry in the lane that owns it
+    }
     for (int r0 = 0; r0 < K; r0 += NBT * NPI) {
         int32_t j[NBT];
         float a[NBT];
@@ -286,19 +306,35 @@ __global__ __launch_bounds__(WPB * 64) void spmm_fwd_narrow(const int32_t *__res
             j[b] = __shfl(jl, rr, 64);
             a[b] = __shfl(al, rr, 64);
             if (r >= K || j[b] < 0) a[b] = 0.0f;
-            any = any || a[b] != 0.0f;
+            any = any || (NORM ? j[b] >= 0 : a[b] != 0.0f);
         }
         if (__ballot(any) == 0ull) continue;                     // wave-uniform
         float4 xv[NBT];
+        if constexpr (NORM) {
+            float aj[NBT];
 #pragma unroll
-        for (int b = 0; b < NBT; b++)                            // unconditional gathers (inactive: row 0, weight 0)
-            xv[b] = *reinterpret_cast<const float4 *>(X + (int64_t)(a[b] != 0.0f ? j[b] : 0) * F + 4 * c4);
+            for (int b = 0; b < NBT; b++) {                      // unconditional, clamped: the table entry beside the row gather
+                const int64_t jc = j[b] >= 0 ? j[b] : 0;
+                aj[b] = ainv[jc];
+                xv[b] = *reinterpret_cast<const float4 *>(X + jc * F + 4 * c4);
+            }
+#pragma unroll
+            for (int b = 0; b < NBT; b++) {
+                a[b] = j[b] >= 0 ? __fmul_rn(a[b], aj[b]) : 0.0f;
+                if (c4 == r0 / NPI + b) mine = a[b];             // entry r0 + b * NPI + slot = c4 * NPI + slot
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NBT; b++)                        // unconditional gathers (inactive: row 0, weight 0)
+                xv[b] = *reinterpret_cast<const float4 *>(X + (int64_t)(a[b] != 0.0f ? j[b] : 0) * F + 4 * c4);
+        }
 #pragma unroll
         for (int b = 0; b < NBT; b++) {
             acc.x = fmaf(a[b], xv[b].x, acc.x); acc.y = fmaf(a[b], xv[b].y, acc.y);
             acc.z = fmaf(a[b], xv[b].z, acc.z); acc.w = fmaf(a[b], xv[b].w, acc.w);
         }
     }
+    if constexpr (NORM) ahat_out[ch * 64 + c4 * NPI + slot] = mine;
     }
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1) {
@@ -1167,6 +1203,49 @@ int dgg_ell_spmm_act_fwd_chunked(const int32_t *idx, const float *ahat, const fl
         hipLaunchKernelGGL(act_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Y, n, act);
     }
     return dgg_check_launch("ell_spmm_fwd_chunked");
+}
+
+// Y = act(A X) and ahat from the unnormalised weights (spmm_fwd_narrow<F, CHUNKED, NORM = true>; include/dgg_hip_next.h)
+int dgg_ell_spmm_norm_act_fwd(const int32_t *idx, const float *w, const float *rs_rows, const void *partp_ws, int64_t ncols, const float *X,
+                              int64_t rows, int F, int act, float *Y, float *ahat, void *stream) {
+    if (act != 0 && act != 2) return dgg_set_error(DGG_ERR_ARG, "ell_spmm_norm_act_fwd: act must be 0 (none) or 2 (ReLU)");
+    if (!idx || !w || !rs_rows || !partp_ws || !X || !Y || !ahat) return dgg_set_error(DGG_ERR_ARG, "ell_spmm_norm_act_fwd: missing operand");
+    if ((F != 16 && F != 32 && F != 64) || ((uintptr_t)X % 16) || ((uintptr_t)Y % 16))
+        return dgg_set_error(DGG_ERR_UNSUPPORTED, "ell_spmm_norm_act_fwd: feature width must be 16, 32 or 64 (16-byte aligned rows)");
+    const float *ainv = dgg_partp_ainv(partp_ws, rows, 64, ncols);
+    if (!ainv) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ell_spmm_norm_act_fwd: no payload partition for this shape");
+    if (rows == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+#define DGG_SPMM_NORM(FF)                                                                                                     \
+    hipLaunchKernelGGL((spmm_fwd_narrow<FF, false, true>), dim3(rows_grid(rows)), dim3(WPB * 64), 0, st, idx, w, X, rows, 64, act, Y, \
+                       (const int32_t *)nullptr, rs_rows, ainv, ahat, (int64_t)0)
+    if (F == 64) DGG_SPMM_NORM(64);
+    else if (F == 32) DGG_SPMM_NORM(32);
+    else DGG_SPMM_NORM(16);
+#undef DGG_SPMM_NORM
+    return dgg_check_launch("ell_spmm_norm_act_fwd");
+}
+
+int dgg_ell_spmm_norm_act_fwd_chunked(const int32_t *idx, const float *w, const float *rs_nodes, const void *partp_ws, int64_t ncols,
+                                      const float *X, int64_t rows, const int32_t *cptr, int64_t chunks, int F, int act, float *Y,
+                                      float *ahat, void *stream) {
+    if (act != 0 && act != 2) return dgg_set_error(DGG_ERR_ARG, "ell_spmm_norm_act_fwd_chunked: act must be 0 (none) or 2 (ReLU)");
+    if (!idx || !w || !rs_nodes || !partp_ws || !X || !Y || !ahat || !cptr || chunks < 0 || rows < 0)
+        return dgg_set_error(DGG_ERR_ARG, "ell_spmm_norm_act_fwd_chunked: missing operand");
+    if ((F != 16 && F != 32 && F != 64) || ((uintptr_t)X % 16) || ((uintptr_t)Y % 16))
+        return dgg_set_error(DGG_ERR_UNSUPPORTED, "ell_spmm_norm_act_fwd_chunked: feature width must be 16, 32 or 64 (16-byte aligned rows)");
+    const float *ainv = dgg_partp_ainv(partp_ws, chunks, 64, ncols);
+    if (!ainv) return dgg_set_error(DGG_ERR_UNSUPPORTED, "ell_spmm_norm_act_fwd_chunked: no payload partition for this shape");
+    if (rows == 0 || chunks == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+#define DGG_SPMM_NORM(FF)                                                                                                     \
+    hipLaunchKernelGGL((spmm_fwd_narrow<FF, true, true>), dim3(rows_grid(rows)), dim3(WPB * 64), 0, st, idx, w, X, rows, 64, act, Y, cptr, \
+                       rs_nodes, ainv, ahat, chunks)
+    if (F == 64) DGG_SPMM_NORM(64);
+    else if (F == 32) DGG_SPMM_NORM(32);
+    else DGG_SPMM_NORM(16);
+#undef DGG_SPMM_NORM
+    return dgg_check_launch("ell_spmm_norm_act_fwd_chunked");
 }
 
 // dA [N,K] overwritten; dX (nullable, [Nglobal,F]) accumulated into with atomics

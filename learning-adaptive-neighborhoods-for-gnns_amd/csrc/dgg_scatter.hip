@@ -12,6 +12,7 @@
 // than the entry-wise scatter (N + nnz/64 runs instead of nnz), 16-byte gathers of the source rows.
 #include "dgg_common.h"
 #include "dgg_api_internal.h"
+#include "../../include/dgg_hip_next.h"
 
 using namespace dgg;
 
@@ -203,6 +204,9 @@ struct SoftkArgs {
     // dA_rec[recpos[i*64 + r]] instead -- the map is written by pp_sort, which runs beside the forward aggregation
     const int *recpos;
     const float *dA_rec;
+    // payload partition built with rs_all = rs: its table ainv [ncols] = rs_j^-1/2 (pp_count), read in place of a division and a square
+    // root per lane -- the same bits.  NULL: the expression
+    const float *ainv;
 };
 // The first NB batches (of NPI entries) of the group of entries that starts at rank r0: gathers, squared distances, the scalar chain
 // once per entry in the lane that owns it, accumulation -- see edge_bwd_rows.  NB is a template parameter so that every batch register
@@ -299,7 +303,9 @@ __global__ __launch_bounds__(256) void edge_bwd_rows(const float *__restrict__ x
         const bool live = lane < K && jl >= 0;
         if (sk.normalized) {
             const float rsi = sk.rs[gi];
-            const float ai = __fdiv_rn(1.0f, c_sqrt(rsi)), aj = __fdiv_rn(1.0f, c_sqrt(sk.rs[jl >= 0 ? jl : gi]));
+            const int64_t jx = jl >= 0 ? jl : gi;
+            const float ai = __fdiv_rn(1.0f, c_sqrt(rsi));
+            const float aj = (PAY && sk.ainv) ? sk.ainv[jx] : __fdiv_rn(1.0f, c_sqrt(sk.rs[jx]));    // (kernel-uniform choice)
             float dai = sk.da[gi];
             if (sk.ahat_rows) {
                 const float ah = lane < K ? sk.ahat_rows[i * K + lane] : 0.0f;
@@ -406,7 +412,8 @@ __global__ __launch_bounds__(256) void edge_bwd_rows_chunked(const float *__rest
         float dw = sk.dA[e];
         const float kshift = ki - (float)(64 * (c - cb));
         if (sk.normalized) {
-            const float aj = __fdiv_rn(1.0f, c_sqrt(sk.rs[live ? jl : gi]));
+            const int64_t jx = live ? jl : gi;
+            const float aj = sk.ainv ? sk.ainv[jx] : __fdiv_rn(1.0f, c_sqrt(sk.rs[jx]));             // (kernel-uniform choice)
             if (sk.ahat_rows && sk.ahat_rows[e] == 0.0f) dw = 0.0f;
             dw = dw * ai * aj + drs;
         }
@@ -1803,23 +1810,43 @@ int dgg_partp_build_norm(const int32_t *idx, const float *w, const float *val, c
 
 // the same in two parts, so that a caller can run the second beside other work on another stream: phase 1 = count + scan + fill
 // (ahat is complete, the records sit in bucket order), phase 2 = the per-bucket sort (records in node order + nodeptr: what the
-// backward's column kernels read; the forward aggregation does not need it); phase 0 = both
+// backward's column kernels read; the forward aggregation does not need it); phase 0 = both.
+// Since ABI v6 (include/dgg_hip_next.h): phase 3 = the count pass alone (ainv [ncols] = rs_all^-1/2 and nothing else: all that
+// dgg_ell_spmm_norm_act_fwd reads); phases 4 / 5 = phases 1 / 0 with rs_all and ahat == NULL: ainv is filled, the fill pass writes the
+// records only -- no a_j gathers, no ahat stores (at phases 0..2 rs_all and ahat still go together)
 int dgg_partp_build_phase(const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows, int K, int64_t ncols,
                           const float *rs_all, float *ahat, void *ws, int phase, void *stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (phase < 0 || phase > 2) return dgg_set_error(DGG_ERR_ARG, "partp_build_phase: phase is 0 (all), 1 (count + fill) or 2 (sort)");
+    if (phase < 0 || phase > 5)
+        return dgg_set_error(DGG_ERR_ARG, "partp_build_phase: phase is 0 (all), 1 (count + fill), 2 (sort), 3 (count), 4 / 5 (1 / 0, records only)");
     if (dgg_partp_ws_bytes(rows, K, ncols) == 0 || !ws) return dgg_set_error(DGG_ERR_UNSUPPORTED, "partp_build: unsupported size or NULL workspace");
-    if (!val || !rs_rows) return dgg_set_error(DGG_ERR_ARG, "partp_build: the payload needs the scores and the row sums");
-    if ((rs_all == nullptr) != (ahat == nullptr)) return dgg_set_error(DGG_ERR_ARG, "partp_build_norm: rs_all and ahat go together");
-    if (K == 64 && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(val) |
-                     reinterpret_cast<uintptr_t>(ahat)) % 16))
-        return dgg_set_error(DGG_ERR_ARG, "partp_build: idx / w / val / ahat must be 16-byte aligned");
+    if (phase == 3) {                                            // the count pass alone: ainv [ncols] for the normalising aggregation
+        if (!rs_all || !idx || !w) return dgg_set_error(DGG_ERR_ARG, "partp_build_phase: phase 3 (count) needs idx, w and rs_all");
+        if (K == 64 && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w)) % 16))
+            return dgg_set_error(DGG_ERR_ARG, "partp_build: idx / w must be 16-byte aligned");
+    } else {
+        if (!val || !rs_rows) return dgg_set_error(DGG_ERR_ARG, "partp_build: the payload needs the scores and the row sums");
+        // phases 4 / 5: rs_all WITHOUT ahat -- ainv is filled, the fill pass writes records only (the aggregation normalises)
+        if (phase >= 4 && (!rs_all || ahat)) return dgg_set_error(DGG_ERR_ARG, "partp_build_phase: phases 4 / 5 take rs_all and no ahat");
+        if (phase < 4 && (rs_all == nullptr) != (ahat == nullptr)) return dgg_set_error(DGG_ERR_ARG, "partp_build_norm: rs_all and ahat go together");
+        if (K == 64 && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(val) |
+                         reinterpret_cast<uintptr_t>(ahat)) % 16))
+            return dgg_set_error(DGG_ERR_ARG, "partp_build: idx / w / val / ahat must be 16-byte aligned");
+    }
     if (rows == 0) return 0;
     PartP2 p;
     partp2_layout(p, ws, rows, K, ncols);
     const int nb = (int)p.nb, nwg = (int)p.nwg, pbs = p.width;
     if (phase == 2) {
         hipLaunchKernelGGL(pp_sort<false>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr, pp_builds_map(rows) ? p.recpos : nullptr, nb, pbs, (const int32_t *)nullptr);
+        return dgg_check_launch("partp_build");
+    }
+    if (phase == 3) {
+        switch (pp_threads()) {
+            case 256: hipLaunchKernelGGL(pp_count<256>, dim3((unsigned)nwg), dim3(256), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
+            case 512: hipLaunchKernelGGL(pp_count<512>, dim3((unsigned)nwg), dim3(512), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
+            default: hipLaunchKernelGGL(pp_count<1024>, dim3((unsigned)nwg), dim3(1024), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
+        }
         return dgg_check_launch("partp_build");
     }
 #define DGG_PP_PASS(TT)                                                                                                      \
@@ -1834,7 +1861,7 @@ int dgg_partp_build_phase(const int32_t *idx, const float *w, const float *val, 
         default: DGG_PP_PASS(1024); break;
     }
 #undef DGG_PP_PASS
-    if (phase == 1) return dgg_check_launch("partp_build");
+    if (phase == 1 || phase == 4) return dgg_check_launch("partp_build");
     hipLaunchKernelGGL(pp_sort<false>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr, pp_builds_map(rows) ? p.recpos : nullptr, nb, pbs, (const int32_t *)nullptr);
     return dgg_check_launch("partp_build");
 }
@@ -1851,6 +1878,12 @@ int dgg_partp_internal_ptrs(const void *partp_ws, int64_t rows, int K, int64_t n
     *nodeptr = p.nodeptr;
     *recpos = p.recpos;
     return 0;
+}
+const float *dgg_partp_ainv(const void *partp_ws, int64_t rows, int K, int64_t ncols) {
+    if (!partp_ws || dgg_partp_ws_bytes(rows, K, ncols) == 0) return nullptr;
+    PartP2 p;
+    partp2_layout(p, const_cast<void *>(partp_ws), rows, K, ncols);
+    return p.ainv;
 }
 extern "C" {
 int dgg_partp_describe(int64_t rows, int K, int64_t ncols, int64_t *out6) {
@@ -1945,6 +1978,14 @@ int dgg_softk_edge_bwd_partp_phase(const float *xp, int64_t rows, int h, const i
                                    const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
                                    int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
                                    float *dxp, int out_act, int phase, void *stream) {
+    return dgg_softk_edge_bwd_partp_tab(xp, rows, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, K, row0, t, perturb, mode, normalized, partp_ws,
+                                        ncols, rowinfo_ws, dk, dxp, out_act, phase, 0, stream);
+}
+// ... and with a_j of the row kernel from the partition's ainv table (ainv_table = 1: the partition was built with rs_all = rs)
+int dgg_softk_edge_bwd_partp_tab(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
+                                 const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
+                                 int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
+                                 float *dxp, int out_act, int phase, int ainv_table, void *stream) {
     if (phase < 0 || phase > 2) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_phase: phase is 0 (all), 1 (rows) or 2 (nodes)");
     if (mode != 0 && mode != 1) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: mode must be 0 (k_times) or 1 (k_only)");
     if (out_act != 0 && (out_act != 1 || mode != 0))             // (mode 1 launches no node kernel: nothing would apply the mask)
@@ -1962,7 +2003,7 @@ int dgg_softk_edge_bwd_partp_phase(const float *xp, int64_t rows, int h, const i
     PartP2 p;
     partp2_layout(p, const_cast<void *>(partp_ws), rows, K, ncols);
     const SoftkArgs sk{k, rs, dA, da, mode, normalized, nullptr, dk, ahat_rows, reinterpret_cast<float4 *>(rowinfo_ws),
-                       dA ? nullptr : p.recpos, dA_rec};
+                       dA ? nullptr : p.recpos, dA_rec, (ainv_table && normalized) ? p.ainv : nullptr};
     const unsigned gr = (unsigned)((rows + 3) / 4);
     const bool grouped = node_groups(rows * K, ncols);
     const unsigned nmain = (unsigned)((ncols + 3) / 4);
@@ -1998,16 +2039,31 @@ int dgg_partp_build_chunked(const int32_t *idx, const float *w, const float *val
                             int64_t ncols, const float *rs_all, float *ahat, void *ws, int phase, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const int K = 64;
-    if (phase < 0 || phase > 2) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: phase is 0 (all), 1 (count + fill) or 2 (sort)");
+    // (phases 3, 4 / 5: as dgg_partp_build_phase -- the count pass alone; phases 1 / 0 with rs_all and no ahat, records only)
+    if (phase < 0 || phase > 5)
+        return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: phase is 0 (all), 1 (count + fill), 2 (sort), 3 (count), 4 / 5 (1 / 0, records only)");
     if (dgg_partp_ws_bytes(chunks, K, ncols) == 0 || !ws) return dgg_set_error(DGG_ERR_UNSUPPORTED, "partp_build_chunked: unsupported size or NULL workspace");
-    if (!val || !rs_nodes || !cnode) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: the payload needs the scores, the row sums and the chunk nodes");
-    if ((rs_all == nullptr) != (ahat == nullptr)) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: rs_all and ahat go together");
-    if ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(val) | reinterpret_cast<uintptr_t>(ahat)) % 16)
+    if (phase == 3) {
+        if (!rs_all || !idx || !w) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: phase 3 (count) needs idx, w and rs_all");
+    } else {
+        if (!val || !rs_nodes || !cnode) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: the payload needs the scores, the row sums and the chunk nodes");
+        if (phase >= 4 && (!rs_all || ahat)) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: phases 4 / 5 take rs_all and no ahat");
+        if (phase < 4 && (rs_all == nullptr) != (ahat == nullptr)) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: rs_all and ahat go together");
+    }
+    if ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | (phase == 3 ? 0 : reinterpret_cast<uintptr_t>(val)) | reinterpret_cast<uintptr_t>(ahat)) % 16)
         return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: idx / w / val / ahat must be 16-byte aligned");
     if (chunks == 0) return 0;
     PartP2 p;
     partp2_layout(p, ws, chunks, K, ncols);
     const int nb = (int)p.nb, nwg = (int)p.nwg, pbs = p.width;
+    if (phase == 3) {
+        switch (pp_threads()) {
+            case 256: hipLaunchKernelGGL(pp_count<256>, dim3((unsigned)nwg), dim3(256), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
+            case 512: hipLaunchKernelGGL(pp_count<512>, dim3((unsigned)nwg), dim3(512), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
+            default: hipLaunchKernelGGL(pp_count<1024>, dim3((unsigned)nwg), dim3(1024), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
+        }
+        return dgg_check_launch("partp_build_chunked");
+    }
     if (phase != 2) {
 #define DGG_PP_PASS(TT)                                                                                                      \
     hipLaunchKernelGGL(pp_count<TT>, dim3((unsigned)nwg), dim3(TT), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, \
@@ -2022,7 +2078,7 @@ int dgg_partp_build_chunked(const int32_t *idx, const float *w, const float *val
         }
 #undef DGG_PP_PASS
     }
-    if (phase != 1)
+    if (phase != 1 && phase != 4)
         hipLaunchKernelGGL(pp_sort<true>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr,
                            (int *)nullptr, nb, pbs, cnode);
     return dgg_check_launch("partp_build_chunked");
@@ -2067,6 +2123,14 @@ int dgg_softk_edge_bwd_partp_chunked(const float *xp, int64_t rows, const int32_
                                      const float *k, const float *rs, const float *dA, const float *dA_rec, const float *da, const float *ahat_rows,
                                      int64_t row0, float t, int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols,
                                      float *rowinfo_ws, float *dk, float *dxp, int out_act, int phase, void *stream) {
+    return dgg_softk_edge_bwd_partp_chunked_tab(xp, rows, cptr, chunks, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, row0, t, perturb, mode, normalized,
+                                                partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, phase, 0, stream);
+}
+int dgg_softk_edge_bwd_partp_chunked_tab(const float *xp, int64_t rows, const int32_t *cptr, int64_t chunks, int h, const int32_t *idx,
+                                         const float *val, const float *k, const float *rs, const float *dA, const float *dA_rec,
+                                         const float *da, const float *ahat_rows, int64_t row0, float t, int perturb, int mode,
+                                         int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk, float *dxp,
+                                         int out_act, int phase, int ainv_table, void *stream) {
     const int K = 64;
     if (phase < 0 || phase > 2) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: phase is 0 (all), 1 (rows) or 2 (nodes)");
     if (mode != 0 && mode != 1) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: mode must be 0 (k_times) or 1 (k_only)");
@@ -2079,7 +2143,8 @@ int dgg_softk_edge_bwd_partp_chunked(const float *xp, int64_t rows, const int32_
     hipStream_t st = (hipStream_t)stream;
     PartP2 p;
     partp2_layout(p, const_cast<void *>(partp_ws), chunks, K, ncols);
-    const SoftkArgs sk{k, rs, dA, da, mode, normalized, nullptr, dk, ahat_rows, reinterpret_cast<float4 *>(rowinfo_ws), nullptr, dA_rec};
+    const SoftkArgs sk{k, rs, dA, da, mode, normalized, nullptr, dk, ahat_rows, reinterpret_cast<float4 *>(rowinfo_ws), nullptr, dA_rec,
+                       (ainv_table && normalized) ? p.ainv : nullptr};
     const unsigned gr = (unsigned)((rows + 3) / 4);
     const unsigned nmain = (unsigned)((ncols + 3) / 4);
     const bool split = node_split(ncols);

@@ -1360,6 +1360,38 @@ def spmm_fwd(idx, ahat, X, act=ACT_NONE, layout=None):
     return Y
 
 
+SPMM_NORM_WIDTHS = (16, 32, 64)
+
+
+def spmm_norm_fwd(idx, w, rs_rows, partp, X, act=ACT_NONE, layout=None):
+    """(Y, ahat) = (act(A X), the normalised adjacency rs_i^-1/2 w rs_j^-1/2) from the UNNORMALISED weights w [rows,64]: the aggregation
+    forms ahat itself from the table rs_j^-1/2 in `partp` (partp_build(..., rs_all, want_ahat=False)) -- the bits of partp_build's
+    ahat and of spmm_fwd on it.  rs_rows: the own rows' sums (per node on chunked rows).  None when the kernel does not cover the
+    shape (K = 64, X [ncols, 16 / 32 / 64], 16-byte aligned)."""
+    N, K = idx.shape
+    X, w = _chk(X), _chk(w)
+    F = X.shape[1]
+    if (partp is None or not partp.has_ainv or K != 64 or F not in SPMM_NORM_WIDTHS or X.data_ptr() % 16 or partp.rows != N
+            or X.shape[0] != partp.ncols):
+        return None
+    wide = layout is not None and layout.wide
+    rows = layout.rows if wide else N
+    Y = torch.empty((rows, F), device=idx.device, dtype=torch.float32)
+    ahat = torch.empty((N, K), device=idx.device, dtype=torch.float32)
+    pe = _probe_begin()
+    if wide:
+        assert N == layout.chunks and rs_rows.shape[0] == rows
+        _lib.check(_lib.lib().dgg_ell_spmm_norm_act_fwd_chunked(_ptr(idx), _ptr(w), _ptr(_chk(rs_rows)), _ptr(partp.ws), partp.ncols, _ptr(X), rows,
+                                                                _ptr(layout.cptr), N, F, act, _ptr(Y), _ptr(ahat), _stream()),
+                   "ell_spmm_norm_act_fwd_chunked")
+    else:
+        assert rs_rows.shape[0] == N
+        _lib.check(_lib.lib().dgg_ell_spmm_norm_act_fwd(_ptr(idx), _ptr(w), _ptr(_chk(rs_rows)), _ptr(partp.ws), partp.ncols, _ptr(X), N, F, act,
+                                                        _ptr(Y), _ptr(ahat), _stream()), "ell_spmm_norm_act_fwd")
+    _probe_end("spmm_fwd", pe)
+    return Y, ahat
+
+
 def act_bwd(y, dy, act):
     """dy * act'(y), elementwise"""
     y, dy = _chk(y), _chk(dy)
@@ -1453,6 +1485,7 @@ class PartP:
 
     def __init__(self, ws, rows, K, ncols, layout=None):
         self.ws, self.rows, self.K, self.ncols = ws, rows, K, ncols
+        self.has_ainv = False                # built with rs_all: the workspace holds rs_j^-1/2 of every destination node
         self.layout = layout                 # ChunkLayout when the block is the [chunks,64] arrays of chunked rows (rows = chunks)
 
 
@@ -1468,18 +1501,38 @@ def partp_records(partp):
     return nodeptr, recs
 
 
-def partp_build(idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None):
+def partp_build(idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None, want_ahat=True):
     """Payload partition of the active ELL entries by destination node: records carry w * rs_i^-1/2 and the score, there is no
     slot map.  Returns None when it does not apply.  rs_all [ncols] (row sums of every node): normalize_adj is fused and the
     result is (partition, ahat [rows,K]).  phase=1: count + scan + fill only (ahat complete); finish with partp_sort(), possibly on
     another stream -- the sorted records are read by the backward's column kernels only.
     layout (ChunkLayout, wide): idx / w / val are [chunks,64], rs_rows [layout.rows] per NODE; the sorted records then carry the
-    source node of their chunk in place of the destination (dgg_partp_build_chunked)."""
+    source node of their chunk in place of the destination (dgg_partp_build_chunked).
+    want_ahat=False (with rs_all): the partition keeps only its table rs_j^-1/2 and the fill pass writes records alone -- no ahat; the
+    result is (partition, None) and spmm_norm_fwd() normalises inside the aggregation.  phase=3 (want_ahat=False): the count pass
+    alone, i.e. that table and nothing else -- all spmm_norm_fwd reads; such a partition cannot be sorted."""
     N, K = idx.shape
     nbytes = int(_lib.lib().dgg_partp_ws_bytes(N, K, ncols))
     if nbytes == 0:
         return None
     ws = torch.empty((nbytes,), device=idx.device, dtype=torch.uint8)
+    if not want_ahat:
+        assert rs_all is not None and phase in (0, 1, 3), "want_ahat=False: rs_all is required; phase 0, 1 or 3 (count only)"
+        wide = layout is not None and layout.wide
+        assert not wide or (K == 64 and N == layout.chunks and rs_rows.shape[0] == layout.rows)
+        cphase = {0: 5, 1: 4, 3: 3}[phase]          # (the C entries' phases 5 / 4: phases 0 / 1 with rs_all and no ahat)
+        pe = _probe_begin()
+        if wide:
+            _lib.check(_lib.lib().dgg_partp_build_chunked(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, _ptr(layout.cnode), ncols,
+                                                          _ptr(_chk(rs_all)), None, _ptr(ws), cphase, _stream()), "partp_build_chunked")
+        else:
+            _lib.check(_lib.lib().dgg_partp_build_phase(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, K, ncols,
+                                                        _ptr(_chk(rs_all)), None, _ptr(ws), cphase, _stream()), "partp_build_phase")
+        _probe_end("pp_count" if phase == 3 else "pp_fill", pe)
+        part = PartP(ws, N, K, ncols, layout if wide else None)
+        part.has_ainv = True
+        part.args = (idx, w, val, rs_rows, rs_all, None) if phase == 1 else None
+        return part, None
     if layout is not None and layout.wide:
         assert K == 64 and N == layout.chunks and rs_rows.shape[0] == layout.rows
         ahat = torch.empty((N, K), device=idx.device, dtype=torch.float32) if rs_all is not None else None
@@ -1487,6 +1540,7 @@ def partp_build(idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None):
                                                       _ptr(None if rs_all is None else _chk(rs_all)), _ptr(ahat), _ptr(ws), int(phase), _stream()),
                    "partp_build_chunked")
         part = PartP(ws, N, K, ncols, layout)
+        part.has_ainv = rs_all is not None
         part.args = (idx, w, val, rs_rows, rs_all, ahat) if phase == 1 else None
         return part if rs_all is None else (part, ahat)
     if rs_all is None:
@@ -1498,6 +1552,7 @@ def partp_build(idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None):
     _lib.check(_lib.lib().dgg_partp_build_phase(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, K, ncols, _ptr(_chk(rs_all)),
                                                 _ptr(ahat), _ptr(ws), int(phase), _stream()), "partp_build_norm")
     part = PartP(ws, N, K, ncols)
+    part.has_ainv = True
     part.args = (idx, w, val, rs_rows, rs_all, ahat) if phase == 1 else None
     return part, ahat
 
@@ -1505,14 +1560,19 @@ def partp_build(idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None):
 def partp_sort(part):
     """second part of partp_build(phase=1): the per-bucket sort, on the CURRENT stream"""
     idx, w, val, rs_rows, rs_all, ahat = part.args
+    if ahat is None:                         # (built with want_ahat=False; the sort reads neither)
+        rs_all = None
+    pe = _probe_begin()
     if part.layout is not None:
         _lib.check(_lib.lib().dgg_partp_build_chunked(_ptr(idx), _ptr(w), _ptr(val), _ptr(rs_rows), part.rows, _ptr(part.layout.cnode), part.ncols,
                                                       _ptr(rs_all), _ptr(ahat), _ptr(part.ws), 2, _stream()), "partp_sort")
         part.args = None
+        _probe_end("pp_sort", pe)
         return
     _lib.check(_lib.lib().dgg_partp_build_phase(_ptr(idx), _ptr(w), _ptr(val), _ptr(rs_rows), part.rows, part.K, part.ncols, _ptr(rs_all),
                                                 _ptr(ahat), _ptr(part.ws), 2, _stream()), "partp_sort")
     part.args = None
+    _probe_end("pp_sort", pe)
 
 
 def partp_gather(partp, dA):
@@ -1562,12 +1622,14 @@ def conv_bwd_cols_p(idx, H, G, partp, rs, zero_dA=True, dA_ext=None, want_dA=Tru
 
 
 def softk_edge_bwd_p(xp, idx, val, k, dA, dA_rec, rs, da, row0, t, perturb, mode, normalized, partp, ahat_rows=None, out_act=ACT_NONE,
-                     phase=0, state=None):
+                     phase=0, state=None, ainv_table=None):
     """softk_edge_bwd on a payload partition -> dxp [Nglobal,h], dk [N]; None when it does not apply.  out_act=ACT_LEAKY (mode 0):
     dxp comes back multiplied by LeakyReLU'(xp), the gradient of the pre-activation of the layer that produced xp.
     phase=1: the row kernel only -> (dxp, dk, state): dk is complete (the k-net backward can start, e.g. on another stream);
     phase=2 with that `state`: the per-destination kernel completes dxp.  dA=None (normalised form with ahat_rows): the row kernel
-    takes an entry's cotangent from dA_rec through the partition's slot -> record map (conv_bwd_cols_p(want_dA=False))."""
+    takes an entry's cotangent from dA_rec through the partition's slot -> record map (conv_bwd_cols_p(want_dA=False)).
+    ainv_table: the row kernel reads rs_j^-1/2 from the partition's table instead of forming it per lane (the same bits; the partition
+    must have been built with rs_all = rs).  None = whenever the partition has the table."""
     xp = _chk(xp)
     Ng, h = xp.shape
     N, K = idx.shape
@@ -1575,6 +1637,8 @@ def softk_edge_bwd_p(xp, idx, val, k, dA, dA_rec, rs, da, row0, t, perturb, mode
         return None
     lay = partp.layout
     nrows = N if lay is None else lay.rows
+    tab = int(partp.has_ainv if ainv_table is None else ainv_table)
+    assert not tab or partp.has_ainv, "softk_edge_bwd_p: this partition was built without rs_all, it has no rs^-1/2 table"
     if phase == 2:
         dxp, dk, rowinfo = state
     else:
@@ -1585,18 +1649,18 @@ def softk_edge_bwd_p(xp, idx, val, k, dA, dA_rec, rs, da, row0, t, perturb, mode
     pe = _probe_begin()
     if lay is not None:                          # chunked rows: one wavefront per node walks its chunks; rowinfo per chunk
         assert dA is not None and K == 64
-        _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_chunked(_ptr(xp), nrows, _ptr(lay.cptr), N, h, _ptr(idx), _ptr(_chk(val)), _ptr(_chk(k)), _ptr(rs),
-                                                               _ptr(_chk(dA)), _ptr(dA_rec), _ptr(da), _ptr(None if ahat_rows is None else _chk(ahat_rows)),
-                                                               row0, t, int(perturb), mode, int(normalized), _ptr(partp.ws), Ng, _ptr(rowinfo), _ptr(dk),
-                                                               _ptr(dxp), int(out_act), int(phase), _stream()), "softk_edge_bwd_partp_chunked")
+        _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_chunked_tab(_ptr(xp), nrows, _ptr(lay.cptr), N, h, _ptr(idx), _ptr(_chk(val)), _ptr(_chk(k)), _ptr(rs),
+                                                                   _ptr(_chk(dA)), _ptr(dA_rec), _ptr(da), _ptr(None if ahat_rows is None else _chk(ahat_rows)),
+                                                                   row0, t, int(perturb), mode, int(normalized), _ptr(partp.ws), Ng, _ptr(rowinfo), _ptr(dk),
+                                                                   _ptr(dxp), int(out_act), int(phase), tab, _stream()), "softk_edge_bwd_partp_chunked")
         _probe_end("edge_bwd" if phase == 0 else ("edge_bwd_rows" if phase == 1 else "edge_bwd_node"), pe)
         if phase == 1:
             return dxp, dk, (dxp, dk, rowinfo)
         return dxp, dk
-    _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_phase(_ptr(xp), N, h, _ptr(idx), _ptr(_chk(val)), _ptr(_chk(k)), _ptr(rs), _ptr(None if dA is None else _chk(dA)),
-                                                         _ptr(dA_rec), _ptr(da), _ptr(None if ahat_rows is None else _chk(ahat_rows)), K, row0, t,
-                                                         int(perturb), mode, int(normalized), _ptr(partp.ws), Ng, _ptr(rowinfo), _ptr(dk),
-                                                         _ptr(dxp), int(out_act), int(phase), _stream()), "softk_edge_bwd_partp")
+    _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_tab(_ptr(xp), N, h, _ptr(idx), _ptr(_chk(val)), _ptr(_chk(k)), _ptr(rs), _ptr(None if dA is None else _chk(dA)),
+                                                       _ptr(dA_rec), _ptr(da), _ptr(None if ahat_rows is None else _chk(ahat_rows)), K, row0, t,
+                                                       int(perturb), mode, int(normalized), _ptr(partp.ws), Ng, _ptr(rowinfo), _ptr(dk),
+                                                       _ptr(dxp), int(out_act), int(phase), tab, _stream()), "softk_edge_bwd_partp")
     _probe_end("edge_bwd" if phase == 0 else ("edge_bwd_rows" if phase == 1 else "edge_bwd_node"), pe)
     if phase == 1:
         return dxp, dk, (dxp, dk, rowinfo)

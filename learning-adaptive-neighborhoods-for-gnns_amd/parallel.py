@@ -180,7 +180,10 @@ class KernelContract:
     def rsym_status(self, ws, N, rows=None):
         return None
 
-    def partp_build(self, idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None):
+    def partp_build(self, idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None, want_ahat=True):
+        return None
+
+    def spmm_norm_fwd(self, idx, w, rs_rows, partp, X, act=0, layout=None):
         return None
 
     def partp_sort(self, part):
@@ -203,7 +206,7 @@ class KernelContract:
         return None
 
     def softk_edge_bwd_p(self, xp, idx, val, k, dA, dA_rec, rs, da, row0, t, perturb, mode, normalized, partp, ahat_rows=None, out_act=0,
-                         phase=0, state=None):
+                         phase=0, state=None, ainv_table=None):
         return None
 
 
@@ -290,6 +293,9 @@ class ShardedDGGConv:
         self.overlap = ov != "0"
         self.overlap_sort, self.overlap_knet = ov in ("1", "3"), ov in ("1", "2")
         self._side = None
+        # normalize_adj inside the forward aggregation (partp_build(want_ahat=False) + spmm_norm_fwd) instead of the partition's fill
+        # pass; DGG_NORM_IN_SPMM=0 keeps the fill pass's ahat + spmm_fwd
+        self.norm_in_spmm = os.environ.get("DGG_NORM_IN_SPMM", "1") != "0"
         self.K, self.t, self.noise_mode, self.seed, self.mode, self.algo, self.x_grad = K, t, noise_mode, seed, mode, algo, x_grad
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -518,7 +524,15 @@ class ShardedDGGConv:
         self._partition(s, rs_local)
         s["H"] = self._gathered_H(H, g_H)
         lkw = {} if s["layout"] is None else {"layout": s["layout"]}
-        s["Z"] = self.kern.spmm_fwd(s["idx"], s["ahat"], s["H"], 2, **lkw)    # relu(A (x Wc))
+        got = None
+        if s["ahat"] is None:                       # the partition kept rs_j^-1/2 only: the aggregation normalises and returns ahat
+            got = self.kern.spmm_norm_fwd(s["idx"], s["w"], rs_local, s["partp"], s["H"], 2, **lkw)
+            if got is None:                         # (e.g. a gathered H that is not 16-byte aligned: the normalisation kernel, then the pair)
+                s["ahat"] = self.kern.normalize_fwd(s["idx"], s["w"], s["rs"], self.r0)
+        if got is not None:
+            s["Z"], s["ahat"] = got
+        else:
+            s["Z"] = self.kern.spmm_fwd(s["idx"], s["ahat"], s["H"], 2, **lkw)    # relu(A (x Wc))
         s["gen"] = self._fwd_gen
         self.saved = s
         return s["Z"]
@@ -688,9 +702,13 @@ class ShardedDGGConv:
         """destination-bucket partition of the active entries: the backward's column-side terms run on it (no atomics).  Reads s: idx,
         w, val, rs, layout, xp, H_loc.  Writes s: partp (payload form -- records carry w rs_i^-1/2 and the score, no slot map,
         normalize_adj fused into its fill pass -- when the namespace offers it and covers the shape), else part (index form), ahat,
-        partp_sorted (False: want_backward was off and the sort was not launched), side_join (the sort runs on the side stream)."""
+        partp_sorted (False: want_backward was off and the sort was not launched), side_join (the sort runs on the side stream).
+        With norm_in_spmm, where the namespace normalises inside the aggregation (spmm_norm_fwd; 64-rank lists or chunked rows, conv
+        width 16 / 32 / 64) the fill pass writes records only and ahat stays None for forward() to take from spmm_norm_fwd; with
+        want_backward off only the partition's count pass runs (the rs_j^-1/2 table).  DGG_NORM_IN_SPMM=0: ahat from the fill pass."""
         kern, rs, lay = self.kern, s["rs"], s["layout"]
         use_p = s["xp"].shape[1] in KERNEL_WIDTHS and s["H_loc"].shape[1] in KERNEL_WIDTHS and self.mode in (0, 1)
+        use_n = use_p and self.norm_in_spmm and s["idx"].shape[1] == 64 and s["H_loc"].shape[1] in (16, 32, 64)
         ov = use_p and self.overlap and self.overlap_sort and s["idx"].is_cuda
         # want_backward = False (set by the autograd node under torch.no_grad() / frozen parameters): the per-bucket sort of the
         # partition -- read by the backward's column kernels only -- is not launched at all (ADVICE round 4: an eval forward used to
@@ -698,7 +716,9 @@ class ShardedDGGConv:
         nobwd = use_p and not self.want_backward
         lkw = {} if lay is None else {"layout": lay}
         got = None
-        if use_p and (ov or nobwd):
+        if use_n:
+            got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, phase=3 if nobwd else (1 if ov else 0), want_ahat=False, **lkw)
+        elif use_p and (ov or nobwd):
             got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, phase=1, **lkw)
         elif use_p:
             got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, **lkw)
@@ -717,7 +737,7 @@ class ShardedDGGConv:
                 s["partp"].ws.record_stream(side)
             s["side_join"] = True
         s["part"] = kern.part_build(s["idx"], s["w"], self.N) if s["partp"] is None else None
-        if s["ahat"] is None:
+        if s["ahat"] is None and not (use_n and got is not None):
             s["ahat"] = kern.normalize_fwd(s["idx"], s["w"], rs, self.r0)
 
     def _gathered_H(self, H, g_H):
