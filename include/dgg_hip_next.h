@@ -86,6 +86,24 @@ int dgg_softk_edge_bwd_partp_chunked_tab(const float *xp, int64_t rows, const in
                                          int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk, float *dxp,
                                          int out_act, int phase, int ainv_table, void *stream);
 
+/* ==== block project_knet ==== (dgg_amd._lib.NEXT_BLOCKS["project_knet"]) */
+
+/* ---- the dense prologue of the forward in one launch: several layers on one input + the learned degree ---------------------------
+ * y_s [N, out_s] = act_s(x W_s^T + b_s) for nseg <= 8 layers that read x [N,d] (dgg_linear_fwd_multi), each weight read from its OWN tensor
+ * -- W / b / y are HOST arrays of nseg device pointers, b or b[s] may be NULL, seg_layout[s] 0: W_s [out_s,d], 1: W_s [d,out_s] -- and
+ * k [N], u [N] (u nullable) = dgg_knet_x_fwd_mfma on layer knet_seg's output (h = 64: W1 [32,65], b1 [32], Wmu [16,32], bmu [16], Wp [16],
+ * bp [1]; deg [N], mu_sd [2]), taken from the projection's accumulators instead of a second pass over y_knet_seg.  Every output has the
+ * bits of dgg_linear_pack_weights + dgg_linear_fwd_multi + dgg_knet_x_fwd_mfma: the same k-ordered fmaf chains.
+ * force: -1 = the fused kernel where dgg_linear_fwd_multi takes its persistent kernel (N >= 32768), 0 = never, 1 = at any N.
+ * DGG_ERR_UNSUPPORTED and nothing written -- the caller runs the pair --: force says so; d != 128; a width that is no multiple of 32 or
+ * more than 6 column blocks of 32; a k-net layer that is not 64 wide; layers arranged other than xp | xk | H, xp | xk, xk | H or xk
+ * (64-wide neighbours); x, a y_s or a weight not 16-byte aligned.  DGG_ERR_ARG: a NULL array, nseg / knet_seg / force out of
+ * range.  N == 0 returns 0 without a launch. */
+int dgg_project_knet_fwd(const float *x, int64_t N, int d, int nseg, const float *const *W, const float *const *b, const int *seg_out,
+                         const int *seg_layout, const int *seg_act, float *const *y, int knet_seg, const float *deg, const float *mu_sd,
+                         const float *W1, const float *b1, const float *Wmu, const float *bmu, const float *Wp, const float *bp, float *k,
+                         float *u, int force, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

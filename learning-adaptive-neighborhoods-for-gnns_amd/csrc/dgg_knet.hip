@@ -12,6 +12,7 @@
 // node's activations in registers, the (wave-uniform) weights through scalar loads -- full-rate v_fma, no cross-lane
 // traffic.  Other shapes: one wavefront per node, lane o computes output unit o.
 #include "dgg_common.h"
+#include "dgg_knet_chain.h"
 #include <algorithm>
 #include "dgg_api_internal.h"
 
@@ -298,9 +299,10 @@ __global__ __launch_bounds__(512) void knet_x_fwd_reg(const float *__restrict__ 
                                                       const float *__restrict__ b1, const float *__restrict__ Wmu,
                                                       const float *__restrict__ bmu, const float *__restrict__ Wp,
                                                       const float *__restrict__ bp, float *__restrict__ k, float *__restrict__ u_save) {
-    constexpr int H2 = H / 2, H4 = H / 4, XR = H / 2, S1 = H / 2 + 1, S2 = H2 / 2 + 1;
+    using Chain = dgg::KnetChain<H>;
+    constexpr int H4 = H / 4, XR = H / 2;
     // the weights in operand order, once per workgroup of eight wavefronts
-    __shared__ float wsh[(S1 + S2) * 64];
+    __shared__ float wsh[Chain::LDS_FLOATS];
     const int lane = threadIdx.x & 63, wave = dgg::wave_id(), li = lane & 31, hh = lane >> 5;
     constexpr int WAVES = 8;
     const int64_t blk = (int64_t)blockIdx.x * WAVES + wave;
@@ -318,73 +320,23 @@ __global__ __launch_bounds__(512) void knet_x_fwd_reg(const float *__restrict__ 
     }
     const float dg = deg[nc];
     const float mu = mu_sd[0], sd = mu_sd[1];
-    for (int e = threadIdx.x; e < (S1 + S2) * 64; e += WAVES * 64) {
-        const int l = e & 63, sI = e >> 6, o = l & 31, c = 2 * (sI < S1 ? sI : sI - S1) + (l >> 5);
-        float v;
-        if (sI < S1) v = o < H2 ? (c <= H ? W1[o * (H + 1) + c] : b1[o]) : 0.0f;
-        else v = o < H4 ? (c < H2 ? Wmu[o * H2 + c] : (c == H2 ? bmu[o] : 0.0f)) : 0.0f;
-        wsh[e] = v;
-    }
+    Chain::template stage<WAVES * 64>(wsh, W1, b1, Wmu, bmu, threadIdx.x);
     __syncthreads();
     if (blk * 32 >= N) return;
-    float w1[S1], w2[S2];
-#pragma unroll
-    for (int sI = 0; sI < S1; sI++) w1[sI] = wsh[sI * 64 + lane];
-#pragma unroll
-    for (int sI = 0; sI < S2; sI++) w2[sI] = wsh[(S1 + sI) * 64 + lane];
     float wp[H4];
 #pragma unroll
     for (int o = 0; o < H4; o++) wp[o] = Wp[o];
     const float bpv = bp[0];
+    float op1[XR];                                               // the layer-1 operands in step order
 #pragma unroll
     for (int t = 0; t < XR / 2; t++) {
         const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(xc[2 * t]), __float_as_uint(xc[2 * t + 1]), false, false);
-        xc[2 * t] = __uint_as_float(r[0]);                       // operand of step t        (k = 2t + half)
-        xc[2 * t + 1] = __uint_as_float(r[1]);                   // operand of step H/4 + t  (k = H/2 + 2t + half)
+        op1[t] = __uint_as_float(r[0]);                          // operand of step t        (k = 2t + half)
+        op1[H / 4 + t] = __uint_as_float(r[1]);                  // operand of step H/4 + t  (k = H/2 + 2t + half)
     }
-    const float nd = __fdiv_rn(__fadd_rn(dg, -mu), __fadd_rn(sd, 1e-5f));
-    kf32x16 a1;
-#pragma unroll
-    for (int r = 0; r < 16; r++) a1[r] = 0.0f;
-#pragma unroll
-    for (int sI = 0; sI < S1 - 1; sI++)
-        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[sI], sI < H / 4 ? xc[2 * sI] : xc[2 * (sI - H / 4) + 1], a1, 0, 0, 0);
-    a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[S1 - 1], hh == 0 ? nd : 1.0f, a1, 0, 0, 0);      // k = H: nd, k = H + 1: the bias
-    float zs[16];
-#pragma unroll
-    for (int r = 0; r < 16; r++) zs[r] = a1[r] > 0.0f ? a1[r] : __fmul_rn(0.01f, a1[r]);
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-        const auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(zs[r]), __float_as_uint(zs[r + 1]), false, false);
-        zs[r] = __uint_as_float(q[0]);                           // lower half: o(r)      upper half: o(r) + 1
-        zs[r + 1] = __uint_as_float(q[1]);                       // lower half: o(r) + 4  upper half: o(r) + 5
-    }
-    kf32x16 a2;
-#pragma unroll
-    for (int r = 0; r < 16; r++) a2[r] = 0.0f;
-#pragma unroll
-    for (int sI = 0; sI < S2 - 1; sI++) {
-        const int o = 2 * sI;                                    // (the lower half's k; the upper half's k = o + 1 sits in the same register)
-        const int pr = 4 * (o >> 3) + (o & 2);
-        a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[sI], (o & 4) ? zs[pr + 1] : zs[pr], a2, 0, 0, 0);
-    }
-    a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[S2 - 1], hh == 0 ? 1.0f : 0.0f, a2, 0, 0, 0);     // k = H2: the bias
-    // k_project: one lane per node gathers the h/4 values of m (its own rows and the other half's) and runs the ascending chain
-    float m[16];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const float other = __uint_as_float(dgg::xor_shfl<32>(__float_as_uint(a2[r]), lane));
-        const int a_mine = (r & 3) + 8 * (r >> 2) + 4 * hh, a_oth = (r & 3) + 8 * (r >> 2) + 4 * (1 - hh);
-        m[a_mine & 15] = a2[r];
-        m[a_oth & 15] = other;
-    }
-    float ak = 0.0f;
-#pragma unroll
-    for (int o = 0; o < H4; o++) ak = __fmaf_rn(m[o], wp[o], ak);
-    const float kp = __fadd_rn(ak, bpv);
-    const float u = __fadd_rn(__fmul_rn(kp, sd), mu);
+    const float u = Chain::run(op1, dg, mu, sd, wsh, wp, bpv, lane);   // (the chain itself: dgg_knet_chain.h, shared with the fused projection)
     if (hh == 0 && valid) {
-        k[n] = __fadd_rn(u > 0.0f ? u : 0.0f, 1.0f);
+        k[n] = Chain::k_of(u);
         if (u_save) u_save[n] = u;
     }
 }

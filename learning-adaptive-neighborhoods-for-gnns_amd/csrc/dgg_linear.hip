@@ -12,6 +12,7 @@
 // floats -> conflict-free ds_read_b32 of the one-float-per-lane MFMA operands).
 #include "dgg_common.h"
 #include "dgg_api_internal.h"
+#include "dgg_knet_chain.h"
 
 #include <cstdlib>
 
@@ -212,16 +213,40 @@ __global__ __launch_bounds__(64 * WAVES, NACC <= 2 ? 4 : 2) void linear_fwd_mfma
 //    dealt one (row block, column block) unit at a time -- a whole extra block on a few SIMDs would cost a full round (3125
 //    blocks of a 100k-row input on 1024 SIMDs: 3 rounds + 53 blocks).
 // Same k-ordered fmaf chain per output as linear_fwd_mfma: bit-identical results.
-template <int D, int NACC>
-__global__ __launch_bounds__(256, 1) void linear_fwd_reg(const float *__restrict__ x, int64_t N, const float *__restrict__ W,
-                                                         const float *__restrict__ b, LinSegs segs, int64_t nrb) {
+//
+// The weights are staged from the layers' OWN tensors (LinW: one pointer, layout and bias per 32-column block), so nothing has to stack
+// them first.  KS >= 0: column blocks KS and KS + 1 are node_encode_for_k's 64 outputs and the kernel goes on to the learned degree
+// (dgm.py:1569-1584) while they are still in the accumulators: after the bias step and the activation -- the values that are stored as
+// xk -- one v_permlane32_swap per register pair turns the two accumulators into the layer-1 operands of the k-net chain
+// (dgg_knet_chain.h, the body knet_x_fwd_reg runs: same operands, same k-ordered chains, same bits), whose weights sit in LDS beside the
+// projection's.  In the remainder the two xk blocks of a row block and the chain are ONE unit (NACC - 1 units per row block): layer 1
+// contracts over all 64 columns, so they have to meet in one wavefront.
+struct LinW {
+    const float *w[8];     // first weight of column block cb: layout 0 W[32][D] rows of D, layout 1 element (j, c) at w[c * ld + j]
+    const float *b[8];     // its 32 biases, or NULL
+    int ld[8];             // layout 1: the layer's width
+    int layout[8];
+};
+struct KnetFwdArgs {
+    const float *deg, *mu_sd, *W1, *b1, *Wmu, *bmu, *Wp, *bp;
+    float *k, *u;          // u nullable
+};
+
+template <int D, int NACC, int KS = -1>
+__global__ __launch_bounds__(256, 1) void linear_fwd_reg(const float *__restrict__ x, int64_t N, LinW lw, int hasb, LinSegs segs,
+                                                         int64_t nrb, KnetFwdArgs kn) {
     constexpr int S = D / 2, XR = D / 2;                         // MFMA steps per output; operand registers per lane
-    __shared__ float wsf[S * NACC * 64];                         // [step][column block][lane]
+    constexpr bool KNET = KS >= 0;
+    constexpr int KH = 64, NU = KNET ? NACC - 1 : NACC;          // k-net width; remainder units per row block
+    using Chain = dgg::KnetChain<KH>;
+    static_assert(!KNET || (KS + 2 <= NACC && D % 4 == 0), "the k-net segment is two column blocks");
+    __shared__ __attribute__((aligned(16))) float wsf[S * NACC * 64 + (KNET ? Chain::LDS_FLOATS : 0)];   // [step][column block][lane], then the k-net's two layers
+    float *const wkn = wsf + S * NACC * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = dgg::wave_id(), li = lane & 31, hh = lane >> 5;
     const int64_t nw = (int64_t)gridDim.x * 4, slot = (int64_t)blockIdx.x * 4 + wave;
     const int64_t nrbf = N / 32;                                 // FULL row blocks (a partial last block is a remainder unit)
     const int64_t nmain = nrbf - nrbf % nw, nfull = nmain / nw;
-    const int64_t R = nrb - nmain, nunits = nfull + (slot < R * NACC ? (R * NACC - slot + nw - 1) / nw : 0);
+    const int64_t R = nrb - nmain, nunits = nfull + (slot < R * NU ? (R * NU - slot + nw - 1) / nw : 0);
     // unit t of this wavefront: a whole row block while t < nfull, then one (row block, column block) of the remainder
     auto unit_rb = [&](int64_t t) {
         if (t < nfull) return slot + t * nw;
@@ -239,22 +264,69 @@ __global__ __launch_bounds__(256, 1) void linear_fwd_reg(const float *__restrict
             dst[4 * q] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w;
         }
     };
-    if (nunits > 0) load_rows(unit_rb(0), xc);                   // in flight while the weights are staged
-#pragma unroll                                                    // (all loads in flight: a rolled loop pays one L2 round trip per pass)
-    for (int it = 0; it < NACC * 32 * (D / 4) / 256; it++) {     // lanes along the output index: conflict-free LDS writes
-        const int e = tid + it * 256;
-        const int j = e % (NACC * 32), q = e / (NACC * 32);
-        const float4 v = *reinterpret_cast<const float4 *>(W + (int64_t)j * D + 4 * q);
-        float *dst = wsf + ((2 * q) * NACC + (j >> 5)) * 64 + (j & 31);
-        dst[0] = v.x; dst[32] = v.y; dst[NACC * 64] = v.z; dst[NACC * 64 + 32] = v.w;
+    // the prior degree of the lane's node, fetched one unit ahead like its row (KS >= 0 only)
+    auto load_deg = [&](int64_t rb) {
+        if constexpr (!KNET) return 0.0f;
+        const int64_t row = rb * 32 + li;
+        return kn.deg[row < N ? row : N - 1];
+    };
+    float dgc = 0.0f, dgn = 0.0f;
+    if (nunits > 0) {                                            // in flight while the weights are staged
+        load_rows(unit_rb(0), xc);
+        dgc = load_deg(unit_rb(0));
     }
-    const bool hasb = b != nullptr;
+    constexpr int WIT = 32 * (D / 4) / 256;                      // 16-byte pieces per thread and column block
+    float4 wv[NACC][WIT];
+#pragma unroll                                                    // (all loads in flight: a rolled loop pays one L2 round trip per pass)
+    for (int a = 0; a < NACC; a++) {                             // lanes along the output index: conflict-free LDS writes
+        const float *wa = lw.w[a];
+        if (lw.layout[a] == 0) {                                 // (block-uniform)
+#pragma unroll
+            for (int it = 0; it < WIT; it++) {
+                const int e = tid + it * 256, jl = e & 31, q = e >> 5;
+                wv[a][it] = *reinterpret_cast<const float4 *>(wa + (int64_t)jl * D + 4 * q);
+            }
+        } else {                                                 // [D, out]: a piece = four consecutive outputs of one k
+            const int64_t ld = lw.ld[a];
+#pragma unroll
+            for (int it = 0; it < WIT; it++) {
+                const int e = tid + it * 256, jq = e & 7, k = e >> 3;
+                wv[a][it] = *reinterpret_cast<const float4 *>(wa + k * ld + 4 * jq);
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < NACC; a++) {
+        if (lw.layout[a] == 0) {
+#pragma unroll
+            for (int it = 0; it < WIT; it++) {
+                const int e = tid + it * 256, jl = e & 31, q = e >> 5;
+                const float4 v = wv[a][it];
+                float *dst = wsf + ((2 * q) * NACC + a) * 64 + jl;
+                dst[0] = v.x; dst[32] = v.y; dst[NACC * 64] = v.z; dst[NACC * 64 + 32] = v.w;
+            }
+        } else {                                                 // (four neighbouring lanes of one half of a step: one 16-byte write)
+#pragma unroll
+            for (int it = 0; it < WIT; it++) {
+                const int e = tid + it * 256, jq = e & 7, k = e >> 3;
+                *reinterpret_cast<float4 *>(wsf + ((k >> 1) * NACC + a) * 64 + (k & 1) * 32 + 4 * jq) = wv[a][it];
+            }
+        }
+    }
     float bj[NACC];
     int actv[NACC];
 #pragma unroll
     for (int a = 0; a < NACC; a++) {
-        bj[a] = hasb ? b[a * 32 + li] : 0.0f;
+        bj[a] = lw.b[a] ? lw.b[a][li] : 0.0f;
         actv[a] = segs.act[a];
+    }
+    // the k-net's constants: its two layers beside the projection's weights, k_project and the degree statistics in registers
+    float kwp[KNET ? Chain::H4 : 1], kbp = 0.0f, kmu = 0.0f, ksd = 0.0f;
+    if constexpr (KNET) {
+        Chain::template stage<256>(wkn, kn.W1, kn.b1, kn.Wmu, kn.bmu, tid);
+#pragma unroll
+        for (int o = 0; o < Chain::H4; o++) kwp[o] = kn.Wp[o];
+        kbp = kn.bp[0]; kmu = kn.mu_sd[0]; ksd = kn.mu_sd[1];
     }
     __syncthreads();
     auto swap_rows = [&]() {
@@ -290,6 +362,40 @@ __global__ __launch_bounds__(256, 1) void linear_fwd_reg(const float *__restrict
             *reinterpret_cast<float4 *>(yb + 8 * q) = act4(make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]), av);
     };
     const float one_or_zero = hh == 0 ? 1.0f : 0.0f;
+    // KS >= 0: the two finished xk accumulators of row block rb (bias in) -> xk leaves as store_block writes it, and the SAME
+    // activated values run the k-net chain -> k, u of the block's nodes
+    auto knet_block = [&](const f32x16 &p0, const f32x16 &p1, int64_t rb, float dg) {
+        if constexpr (KNET) {
+            const int av = actv[KS];                             // (one layer: both blocks carry its activation)
+            float z0[16], z1[16];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float4 v0 = act4(make_float4(p0[4 * q], p0[4 * q + 1], p0[4 * q + 2], p0[4 * q + 3]), av);
+                const float4 v1 = act4(make_float4(p1[4 * q], p1[4 * q + 1], p1[4 * q + 2], p1[4 * q + 3]), av);
+                z0[4 * q] = v0.x; z0[4 * q + 1] = v0.y; z0[4 * q + 2] = v0.z; z0[4 * q + 3] = v0.w;
+                z1[4 * q] = v1.x; z1[4 * q + 1] = v1.y; z1[4 * q + 2] = v1.z; z1[4 * q + 3] = v1.w;
+            }
+            const int64_t n = rb * 32 + li;
+            if (n < N) {
+                float *y0 = segs.y[KS] + n * (int64_t)segs.ld[KS] + 4 * hh, *y1 = segs.y[KS + 1] + n * (int64_t)segs.ld[KS + 1] + 4 * hh;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    *reinterpret_cast<float4 *>(y0 + 8 * q) = make_float4(z0[4 * q], z0[4 * q + 1], z0[4 * q + 2], z0[4 * q + 3]);
+                    *reinterpret_cast<float4 *>(y1 + 8 * q) = make_float4(z1[4 * q], z1[4 * q + 1], z1[4 * q + 2], z1[4 * q + 3]);
+                }
+            }
+            Chain::swap_pairs(z0);
+            Chain::swap_pairs(z1);
+            float op1[KH / 2];                                   // step s: k = 2s / 2s + 1 = output 2s & 31 of block 2s >> 5
+#pragma unroll
+            for (int s = 0; s < KH / 2; s++) op1[s] = 2 * s < 32 ? Chain::from_acc(z0, 2 * s) : Chain::from_acc(z1, 2 * s - 32);
+            const float u = Chain::run(op1, dg, kmu, ksd, wkn, kwp, kbp, lane);
+            if (hh == 0 && n < N) {
+                kn.k[n] = Chain::k_of(u);
+                if (kn.u) kn.u[n] = u;
+            }
+        }
+    };
     // one whole row block
     auto main_block = [&](int64_t rb) {
         f32x16 acc[NACC];
@@ -320,37 +426,65 @@ __global__ __launch_bounds__(256, 1) void linear_fwd_reg(const float *__restrict
             for (int a = 0; a < NACC; a++) acc[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(bj[a] * one_or_zero, one_or_zero, acc[a], 0, 0, 0);
         }
 #pragma unroll
-        for (int a = 0; a < NACC; a++) store_block(acc[a], a, rb);
+        for (int a = 0; a < NACC; a++)
+            if (!KNET || (a != KS && a != KS + 1)) store_block(acc[a], a, rb);
+        if constexpr (KNET) knet_block(acc[KS], acc[KS + 1], rb, dgc);   // last: the other blocks' stores drain under the chain
     };
     int64_t t = 0;
     for (; t < nfull; t++) {
         load_rows(unit_rb(t + 1 < nunits ? t + 1 : t), xn);      // unconditional; in flight during the MFMAs below
+        dgn = load_deg(unit_rb(t + 1 < nunits ? t + 1 : t));
         asm volatile("" ::: "memory");                           // the weights are re-read from LDS per block (hoisted out of this loop
                                                                  //  they would need S*NACC registers and spill)
         swap_rows();
         main_block(unit_rb(t));
 #pragma unroll
         for (int q = 0; q < XR; q++) xc[q] = xn[q];
+        dgc = dgn;
     }
     for (; t < nunits; t++) {                                    // remainder: one (row block, column block) per unit
         const int64_t rb = unit_rb(t);
         load_rows(unit_rb(t + 1 < nunits ? t + 1 : t), xn);
+        dgn = load_deg(unit_rb(t + 1 < nunits ? t + 1 : t));
         asm volatile("" ::: "memory");
         swap_rows();
-        const int a = (int)((slot + (t - nfull) * nw) / R);
-        f32x16 acc;
+        const int j = (int)((slot + (t - nfull) * nw) / R);      // the unit's kind: a column block, or (j == KS) the xk pair + chain
+        if (KNET && j == KS) {
+            f32x16 p0, p1;
 #pragma unroll
-        for (int r = 0; r < 16; r++) acc[r] = 0.0f;
-        const float *wa = wsf + a * 64 + lane;
+            for (int r = 0; r < 16; r++) p0[r] = p1[r] = 0.0f;
+            const float *wa = wsf + (KNET ? KS : 0) * 64 + lane;
 #pragma unroll                                                    // (full: xc must stay in registers)
-        for (int s = 0; s < S; s++) {
-            const float av = s < S / 2 ? xc[2 * s] : xc[2 * (s - S / 2) + 1];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s * NACC * 64], av, acc, 0, 0, 0);
+            for (int s = 0; s < S; s++) {
+                const float av = s < S / 2 ? xc[2 * s] : xc[2 * (s - S / 2) + 1];
+                p0 = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s * NACC * 64], av, p0, 0, 0, 0);
+                p1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s * NACC * 64 + 64], av, p1, 0, 0, 0);
+            }
+            if (hasb) {
+                p0 = __builtin_amdgcn_mfma_f32_32x32x2f32(bj[KNET ? KS : 0] * one_or_zero, one_or_zero, p0, 0, 0, 0);
+                p1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bj[KNET ? KS + 1 : 0] * one_or_zero, one_or_zero, p1, 0, 0, 0);
+            }
+            knet_block(p0, p1, rb, dgc);
+        } else {
+            const int a = KNET && j > KS ? j + 1 : j;
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[r] = 0.0f;
+            const float *wa = wsf + a * 64 + lane;
+#pragma unroll                                                    // (full: xc must stay in registers)
+            for (int s = 0; s < S; s++) {
+                const float av = s < S / 2 ? xc[2 * s] : xc[2 * (s - S / 2) + 1];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s * NACC * 64], av, acc, 0, 0, 0);
+            }
+            if (hasb) {
+                const float *ba = lw.b[a];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32((ba ? ba[li] : 0.0f) * one_or_zero, one_or_zero, acc, 0, 0, 0);
+            }
+            store_block(acc, a, rb);
         }
-        if (hasb) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b[a * 32 + li] * one_or_zero, one_or_zero, acc, 0, 0, 0);
-        store_block(acc, a, rb);
 #pragma unroll
         for (int q = 0; q < XR; q++) xc[q] = xn[q];
+        dgc = dgn;
     }
 }
 
@@ -1060,8 +1194,15 @@ int dgg_linear_fwd_multi(const float *x, int64_t N, int d, const float *Wcat, co
     if (d == 128 && aligned && cb <= 6 && (forced >= 0 ? forced != 0 : N >= 32768)) {
         const int64_t nrb = (N + 31) / 32;
         const unsigned grid = (unsigned)std::min<int64_t>(256, (nrb + 3) / 4);   // one workgroup per CU
+        LinW lw{};
+        for (int c = 0; c < cb; c++) {
+            lw.w[c] = Wcat + (int64_t)c * 32 * d;
+            lw.b[c] = bcat ? bcat + c * 32 : nullptr;
+        }
+        const int hasb = bcat != nullptr;
+        const KnetFwdArgs kn{};
         switch (cb) {
-#define DGG_LIN_REG(NA) case NA: hipLaunchKernelGGL((linear_fwd_reg<128, NA>), dim3(grid), dim3(256), 0, st, x, N, Wcat, bcat, segs, nrb); break
+#define DGG_LIN_REG(NA) case NA: hipLaunchKernelGGL((linear_fwd_reg<128, NA>), dim3(grid), dim3(256), 0, st, x, N, lw, hasb, segs, nrb, kn); break
             DGG_LIN_REG(1); DGG_LIN_REG(2); DGG_LIN_REG(3); DGG_LIN_REG(4); DGG_LIN_REG(5); DGG_LIN_REG(6);
 #undef DGG_LIN_REG
         }
@@ -1098,6 +1239,57 @@ int dgg_linear_fwd_multi(const float *x, int64_t N, int d, const float *Wcat, co
         default: launch_linear_fwd_multi_n<4>(x, N, d, Wcat, bcat, out, segs, st); break;   // 8 blocks = two column tiles of 4
     }
     return dgg_check_launch("linear_fwd_multi");
+}
+
+// dgg_linear_fwd_multi on the layers' own tensors + dgg_knet_x_fwd_mfma on layer `knet_seg`'s output, in ONE launch of the persistent
+// register kernel (dgg_hip_next.h, block project_knet): the bits of that pair.
+int dgg_project_knet_fwd(const float *x, int64_t N, int d, int nseg, const float *const *W, const float *const *b, const int *seg_out,
+                         const int *seg_layout, const int *seg_act, float *const *y, int knet_seg, const float *deg, const float *mu_sd,
+                         const float *W1, const float *b1, const float *Wmu, const float *bmu, const float *Wp, const float *bp, float *k,
+                         float *u, int force, void *stream) {
+    if (N < 0 || d < 1 || nseg < 1 || nseg > 8 || knet_seg < 0 || knet_seg >= nseg || force < -1 || force > 1)
+        return dgg_set_error(DGG_ERR_ARG, "project_knet_fwd: bad shape");
+    if (!x || !W || !seg_out || !seg_layout || !seg_act || !y || !deg || !mu_sd || !W1 || !b1 || !Wmu || !bmu || !Wp || !bp || !k)
+        return dgg_set_error(DGG_ERR_ARG, "project_knet_fwd: a NULL array");
+    if (force == 0 || (force < 0 && N < 32768)) return dgg_set_error(DGG_ERR_UNSUPPORTED, "project_knet_fwd: the two-kernel route is selected");
+    if (d != 128) return dgg_set_error(DGG_ERR_UNSUPPORTED, "project_knet_fwd: d = 128 only");
+    if (seg_out[knet_seg] != 64) return dgg_set_error(DGG_ERR_UNSUPPORTED, "project_knet_fwd: the k-net's input is 64 wide");
+    LinSegs segs{};
+    LinW lw{};
+    int cb = 0, ks = -1;
+    const int hasb = 1;      // as the pair this replaces: a missing bias is a bias of zeros, and the bias step always runs
+    bool aligned = reinterpret_cast<uintptr_t>(x) % 16 == 0;
+    for (int s = 0; s < nseg; s++) {
+        if (seg_out[s] < 32 || seg_out[s] % 32 != 0 || cb + seg_out[s] / 32 > 6)
+            return dgg_set_error(DGG_ERR_UNSUPPORTED, "project_knet_fwd: layer widths must be multiples of 32 with a total of at most 192");
+        if (!W[s] || !y[s] || (seg_layout[s] != 0 && seg_layout[s] != 1)) return dgg_set_error(DGG_ERR_ARG, "project_knet_fwd: bad layer");
+        aligned = aligned && reinterpret_cast<uintptr_t>(y[s]) % 16 == 0 && reinterpret_cast<uintptr_t>(W[s]) % 16 == 0;
+        if (s == knet_seg) ks = cb;
+        for (int q = 0; q < seg_out[s] / 32; q++, cb++) {
+            segs.y[cb] = y[s] + q * 32;
+            segs.ld[cb] = seg_out[s];
+            segs.act[cb] = seg_act[s];
+            lw.w[cb] = seg_layout[s] == 0 ? W[s] + (int64_t)q * 32 * d : W[s] + q * 32;
+            lw.b[cb] = b && b[s] ? b[s] + q * 32 : nullptr;
+            lw.ld[cb] = seg_out[s];
+            lw.layout[cb] = seg_layout[s];
+        }
+    }
+    if (!aligned) return dgg_set_error(DGG_ERR_UNSUPPORTED, "project_knet_fwd: x, y and the weights must be 16-byte aligned");
+    if (N == 0) return 0;
+    const int64_t nrb = (N + 31) / 32;
+    const unsigned grid = (unsigned)std::min<int64_t>(256, (nrb + 3) / 4);       // one workgroup per CU
+    const KnetFwdArgs kn{deg, mu_sd, W1, b1, Wmu, bmu, Wp, bp, k, u};
+    hipStream_t st = (hipStream_t)stream;
+    // (column blocks, first block of the k-net's layer): xp | xk | H, xp | xk, xk | H, xk
+#define DGG_LIN_KNET(NA, KSV) \
+    if (cb == NA && ks == KSV) { \
+        hipLaunchKernelGGL((linear_fwd_reg<128, NA, KSV>), dim3(grid), dim3(256), 0, st, x, N, lw, hasb, segs, nrb, kn); \
+        return dgg_check_launch("project_knet_fwd"); \
+    }
+    DGG_LIN_KNET(6, 2) DGG_LIN_KNET(4, 2) DGG_LIN_KNET(4, 0) DGG_LIN_KNET(2, 0)
+#undef DGG_LIN_KNET
+    return dgg_set_error(DGG_ERR_UNSUPPORTED, "project_knet_fwd: no kernel for this arrangement of layers");
 }
 
 // floats of workspace dgg_linear_bwd needs: N*out for the activation backward + the weight-gradient slab

@@ -189,6 +189,39 @@ def linear_fwd_multi(x, layers):
     return ys
 
 
+# project_knet's route: None = the entry decides (the fused kernel from the N at which linear_fwd_multi takes its persistent kernel),
+# 0 = never (the caller runs linear_fwd_multi + knet_x_fwd_slim), 1 = at any N.  A test sets it in-process.
+PROJECT_KNET_FORCE = None
+
+
+def project_knet(x, layers, knet_seg, deg, mu_sd, W1, b1, Wmu, bmu, Wp, bp, force=None):
+    """linear_fwd_multi(x, layers) AND knet_x_fwd_slim on layer `knet_seg`'s output in one launch (dgg_project_knet_fwd): the k-net chain
+    runs on the projection's accumulators, the weights are read from their own tensors -> ([y_s], k, u) with the bits of the two calls,
+    or None for a shape, alignment or `force` (default: PROJECT_KNET_FORCE) the entry refuses."""
+    x = _chk(x)
+    N, d = x.shape
+    outs = [(W.shape[0] if lay == 0 else W.shape[1]) for W, _, _, lay in layers]
+    force = PROJECT_KNET_FORCE if force is None else force
+    force = -1 if force is None else int(force)
+    if (force == 0 or d != 128 or len(layers) > 8 or any(o % 32 for o in outs) or sum(outs) > 192 or outs[knet_seg] != 64
+            or W1.shape != (32, 65) or Wmu.shape != (16, 32) or x.data_ptr() % 16 or N == 0):
+        return None
+    Ws = [_chk(W) for W, *_ in layers]
+    bs = [None if b is None else _chk(b) for _, b, _, _ in layers]
+    ys = [torch.empty((N, o), device=x.device, dtype=torch.float32) for o in outs]
+    k = torch.empty((N,), device=x.device, dtype=torch.float32)
+    u = torch.empty((N,), device=x.device, dtype=torch.float32)
+    L = _lib.lib()
+    code = L.dgg_project_knet_fwd(_ptr(x), N, d, len(layers), _ptr_array(Ws), _ptr_array(bs), _int_array(outs),
+                                  _int_array([lay for *_, lay in layers]), _int_array([a for _, _, a, _ in layers]), _ptr_array(ys),
+                                  int(knet_seg), _ptr(_chk(deg)), _ptr(mu_sd), _ptr(_chk(W1)), _ptr(_chk(b1)), _ptr(_chk(Wmu)),
+                                  _ptr(_chk(bmu)), _ptr(_chk(Wp)), _ptr(_chk(bp)), _ptr(k), _ptr(u), force, _stream())
+    if code == 2:           # DGG_ERR_UNSUPPORTED (dgg_hip.h): nothing was written
+        return None
+    _lib.check(code, "project_knet_fwd")
+    return ys, k, u
+
+
 def linear_bwd_multi(x, layers):
     """Weight (and bias) gradients of several layers that share the input x, in ONE pass over x:
     layers = [(W, y or None, dy, act, w_layout, need_db), ...] -> [(dW_s, db_s or None)].  The activation derivative of layer s

@@ -124,6 +124,10 @@ class KernelContract:
     def linear_bwd_multi(self, x, layers):
         return None
 
+    # linear_fwd_multi + knet_x_fwd_slim on layer knet_seg's output in one launch -> ([y_s], k, u)
+    def project_knet(self, x, layers, knet_seg, deg, mu_sd, W1, b1, Wmu, bmu, Wp, bp):
+        return None
+
     def zero_pool(self, device, nfloats):
         return None
 
@@ -296,6 +300,8 @@ class ShardedDGGConv:
         # normalize_adj inside the forward aggregation (partp_build(want_ahat=False) + spmm_norm_fwd) instead of the partition's fill
         # pass; DGG_NORM_IN_SPMM=0 keeps the fill pass's ahat + spmm_fwd
         self.norm_in_spmm = os.environ.get("DGG_NORM_IN_SPMM", "1") != "0"
+        # the k-net inside the projection kernel (_project_knet); DGG_FUSE_KNET=0 keeps linear_fwd_multi + knet_x_fwd_slim
+        self.fuse_knet = os.environ.get("DGG_FUSE_KNET", "1") != "0"
         self.K, self.t, self.noise_mode, self.seed, self.mode, self.algo, self.x_grad = K, t, noise_mode, seed, mode, algo, x_grad
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -514,10 +520,15 @@ class ShardedDGGConv:
         which the next forward overwrites."""
         s = {}
         self._fwd_gen += 1
-        xp, H, xk = self._project(x_local, P)
+        fused = self._project_knet(s, x_local, deg_full, P)
+        if fused is None:
+            xp, H, xk = self._project(x_local, P)
+        else:
+            xp, H, xk = fused
         s["xp_loc"], s["H_loc"], s["xk"] = xp, H, xk
         g_xp, g_H = self._start_gathers(xp, H)
-        self._learned_degree(s, deg_full, P)
+        if fused is None:
+            self._learned_degree(s, deg_full, P)
         s["xp"] = xp if g_xp is None else g_xp.get()
         s["idx"], s["val"], s["w"], rs_local = self._search(s, deg_full)
         s["rs"] = self._gather_row_sums(rs_local)
@@ -546,17 +557,41 @@ class ShardedDGGConv:
             return None, _Gather(H, self.N, self.per, self.group, True, self.bufs, "H")
         return None, None
 
-    def _learned_degree(self, s, deg_full, P):
-        """prior-degree statistics (cached on the degree tensor) + k-net.  Reads s: xk.  Writes s: mu_sd, deg_local, k, u and z, feat
-        (None on the matrix-core k-net, whose backward re-runs layer 1)."""
-        kern, xk = self.kern, s["xk"]
+    def _degree_stats(self, s, deg_full):
+        """Writes s: mu_sd (cached on the degree tensor), deg_local -> both"""
         # mean / std of the prior degrees (dgm.py:1569-1570): an INPUT statistic -- recomputed only when the degree tensor changes
         # (keyed on the tensor OBJECT and its version counter, not on its address: a new tensor is always re-read)
         ref = self._stats_ref
         if ref is None or ref() is not deg_full or self._stats_ver != deg_full._version:
-            self._stats_ref, self._stats_ver, self._stats = weakref.ref(deg_full), deg_full._version, kern.degree_stats(deg_full)
-        s["mu_sd"] = mu_sd = self._stats
-        s["deg_local"] = deg_local = deg_full[self.r0:self.r1].contiguous()
+            self._stats_ref, self._stats_ver, self._stats = weakref.ref(deg_full), deg_full._version, self.kern.degree_stats(deg_full)
+        s["mu_sd"] = self._stats
+        s["deg_local"] = deg_full[self.r0:self.r1].contiguous()
+        return s["mu_sd"], s["deg_local"]
+
+    def _project_knet(self, s, x_local, deg_full, P):
+        """The three projections AND the learned degree in one kernel (kern.project_knet) -> xp, H, xk with s: mu_sd, deg_local, k, u,
+        z, feat written as _learned_degree writes them; None = this route takes _project + _learned_degree.  Only where all three
+        projections read the rank's own rows (the first branch of _project) and the k-net is the matrix-core one; DGG_FUSE_KNET=0
+        keeps the two calls."""
+        if not self.fuse_knet or not (self.x_full is None or (self.world == 1 and self.emulate is None)):
+            return None
+        if P["Wk"].shape[0] not in self.kern.KNET_MFMA_WIDTHS:
+            return None
+        Xall = self.x_full if self.x_full is not None else x_local
+        mu_sd, deg_local = self._degree_stats(s, deg_full)
+        got = self.kern.project_knet(Xall, [(P["We"], P["be"], 1, 0), (P["Wk"], P["bk"], 1, 0), (P["Wc"], None, 0, 1)], 1, deg_local, mu_sd,
+                                     P["W1"], P["b1"], P["Wmu"], P["bmu"], P["Wp"].reshape(-1), P["bp"])
+        if got is None:
+            return None
+        (xp, xk, H), s["k"], s["u"] = got
+        s["z"] = s["feat"] = None
+        return xp, H, xk
+
+    def _learned_degree(self, s, deg_full, P):
+        """prior-degree statistics (cached on the degree tensor) + k-net.  Reads s: xk.  Writes s: mu_sd, deg_local, k, u and z, feat
+        (None on the matrix-core k-net, whose backward re-runs layer 1)."""
+        kern, xk = self.kern, s["xk"]
+        mu_sd, deg_local = self._degree_stats(s, deg_full)
         if xk.shape[1] in kern.KNET_MFMA_WIDTHS:
             # k-net on the matrix cores: the forward saves only u; the backward re-runs layer 1 from xk and forms every gradient in one pass
             s["k"], s["u"] = kern.knet_x_fwd_slim(xk, deg_local, mu_sd, P["W1"], P["b1"], P["Wmu"], P["bmu"], P["Wp"].reshape(-1), P["bp"])
