@@ -104,6 +104,43 @@ int dgg_project_knet_fwd(const float *x, int64_t N, int d, int nseg, const float
                          const float *W1, const float *b1, const float *Wmu, const float *bmu, const float *Wp, const float *bp, float *k,
                          float *u, int force, void *stream);
 
+/* ==== block adj_stats ==== (dgg_amd._lib.NEXT_BLOCKS["adj_stats"]) */
+
+/* ---- get_adj_diff_stats on sparse data: the reference's train_stats scalars (dgm.py:1313-1350) --------------------------------------
+ * How far the learned SOFT adjacency (the value before any straight-through replacement: dgm.py:1288 runs before return_hard_or_soft)
+ * has moved from the input graph, and the learned degree from the input degree, of the WHOLE graph (rows [0, rows): row shards refuse a
+ * writer).  The learned rows: cptr == NULL: idx / w [rows,K], K <= 64; cptr [rows+1] given: chunked rows, idx / w [chunks,64] (K = 64),
+ * row i = the chunks [cptr[i], cptr[i+1]), chunks in [cptr[rows], chunks) are not read.  idx < 0 marks an empty slot; the columns of a
+ * row's other slots are distinct.  The input graph in CSR (csr_pattern / AllPairs.prior_csr): rowptr int64 [rows+1], col int32 strictly
+ * ascending within a row, aval float32; k [rows] the learned degrees.  With a_ij the stored input value (0 where nothing is stored) and
+ * w_ij the learned value (0 where not selected, at an empty slot or outside the row's chunks):
+ *   on-edge population   the pairs with a_ij > 0, d = a_ij - w_ij, kept iff d != 0 as a float32 subtraction -- input edges the generator
+ *                        did not select are in it with d = a_ij (dgm.py:1321-1326);
+ *   off-edge population  the pairs with a_ij == 0 (absent, or stored as exactly 0), d = -w_ij, kept iff d != 0 (dgm.py:1322-1328);
+ *                        a stored negative value belongs to neither.
+ * out [10] float32, the layout below: n, mean = sum d / n and the UNBIASED std (n - 1) of either population; in_deg_mean = mean_i sum_j
+ * a_ij; mean and unbiased std of k_diff_i = k_i - sum_j a_ij; k_mean = mean_i k_i.  n == 0 gives a NaN mean and std, n == 1 a NaN std, as
+ * torch.mean / torch.std on what the reference indexes; rows == 0 writes those results (n = 0, the other eight NaN) without a row launch,
+ * and only `out` is read from the arguments.  The counts are exact up to 2^24.
+ * One wavefront per row; moments as (n, mean, M2) in double, merged by Chan's formula in a fixed order (wavefront butterfly, the 16 rows
+ * of a workgroup in ascending order, then one block folds the workgroups' records in a fixed tree); no floating-point atomics: the same
+ * input gives the same bits.  Rounded to float32 only when stored.  ws: 96 * ceil(rows / 16) bytes, 8-byte aligned (those records).
+ * DGG_ERR_ARG and nothing written: K outside 1..64 (K != 64 on chunked rows), rows outside 0 <= rows < 2^31, chunks outside
+ * 0 <= chunks < 2^31, a NULL array (rows > 0) or a NULL out, ws not 8-byte aligned. */
+#define DGG_ADJ_STATS_ON_N 0
+#define DGG_ADJ_STATS_ON_MEAN 1
+#define DGG_ADJ_STATS_ON_STD 2
+#define DGG_ADJ_STATS_OFF_N 3
+#define DGG_ADJ_STATS_OFF_MEAN 4
+#define DGG_ADJ_STATS_OFF_STD 5
+#define DGG_ADJ_STATS_IN_DEG_MEAN 6
+#define DGG_ADJ_STATS_K_DIFF_MEAN 7
+#define DGG_ADJ_STATS_K_DIFF_STD 8
+#define DGG_ADJ_STATS_K_MEAN 9
+#define DGG_ADJ_STATS_COUNT 10
+int dgg_adj_diff_stats(const int32_t *idx, const float *w, int64_t rows, int K, const int32_t *cptr, int64_t chunks, const int64_t *rowptr,
+                       const int32_t *col, const float *aval, const float *k, void *ws, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

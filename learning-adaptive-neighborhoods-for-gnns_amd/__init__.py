@@ -5,7 +5,8 @@ Public surface mirrors the reference's modules:
     dgg_amd.dgm.{DGG_LearnableK_debug, DGG, LearnableKEncoder}               (reference dgm.py)
     dgg_amd.model.{GCNConv, GraphConvolution, DenseGraphConvolution, GCN_DGG, GCN_DGG_00, GCNII_DGG, GCNIIppi_DGG}  (model.py)
     dgg_amd.distributed.{ShardedGCN_DGG, global_nll_loss}                    (GCN_DGG row-sharded across GPUs)
-plus the containers `AllPairs` / `EllAdjacency` / `CsrAdjacency` and the raw kernel wrappers in `dgg_amd.ops`.
+plus the containers `AllPairs` / `EllAdjacency` / `CsrAdjacency`, the raw kernel wrappers in `dgg_amd.ops` and `ScalarLog`, a
+dependency-free writer for the models' `writer=` argument.
 """
 from . import _lib, ops  # noqa: F401
 from .adjacency import AllPairs, CsrAdjacency, EllAdjacency, csr_candidates, csr_pattern, ell_from_dense  # noqa: F401
@@ -15,3 +16,4 @@ from .model import (DenseGraphConv, DenseGraphConvolution, GAT_DGG_00, GAT_DGG_A
                     GCN_DGG_Ablations, GCNConv, GCNII_DGG, GCNIIppi_DGG,
                     GraphConvolution, SAGE_DGG, SAGE_DGG_00)
 from .distributed import ShardedGCN_DGG, global_nll_loss  # noqa: F401
+from .scalar_log import ScalarLog  # noqa: F401

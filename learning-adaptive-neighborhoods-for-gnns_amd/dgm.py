@@ -729,7 +729,7 @@ class DGG_LearnableK_debug(nn.Module):
         st["n"] += 1
         return st["spread"]
 
-    def forward_conv(self, x, in_adj, conv_weight, want_norm=False):
+    def forward_conv(self, x, in_adj, conv_weight, want_norm=False, writer=None, epoch=None):
         """`GCNConv(x, normalize_adj(self(x, in_adj)))` with conv_weight = GCNConv.W [in, out] as one fused autograd node
         (_FusedDGGConvFn) -> (Z, unnormalised EllAdjacency, DETACHED: its values carry no autograd edge -- the loss of the
         reference's training scripts reads the class scores only, train_small_graphs.py:226-230), or None when this configuration
@@ -738,19 +738,25 @@ class DGG_LearnableK_debug(nn.Module):
         want_norm: additionally return the NORMALISED adjacency as a differentiable EllAdjacency for the layers that read the same
         graph after this one (GCN_DGG's second layer): its gradient flows back into the generator through the same node.
         The steps: _fused_outside -> candidates -> _fused_scorer (edge-MLP terms) -> _fused_configure (noise generator, what rows wider
-        than 64 ranks do, flags) -> the node -> _fused_result (what the learned degrees decide after the fact, the returned adjacencies)."""
-        return self._forward_conv(x, in_adj, conv_weight, want_norm)
+        than 64 ranks do, flags) -> the node -> _fused_result (what the learned degrees decide after the fact, the returned adjacencies).
+        writer / epoch: the node is unchanged; after it, in training mode, the reference's scalars values/first_k_* and train_stats/*
+        (dgm.py:1259-1261, 1313-1350) are written from the idx / w / val / k the engine holds (its w are the soft weights: dgg_hard is
+        outside the fused layer) -- one device read-back per logged forward, which a hipGraph capture cannot do: RuntimeError."""
+        return self._forward_conv(x, in_adj, conv_weight, want_norm, writer=writer, epoch=epoch)
 
-    def _forward_conv(self, x, in_adj, conv_weight, want_norm, engine=None):
+    def _forward_conv(self, x, in_adj, conv_weight, want_norm, engine=None, writer=None, epoch=None):
         """forward_conv on the module's own one-GPU engine (engine None) or on the caller's: a ShardedDGGConv of a row shard on replicated
         features (dgg_amd.distributed.ShardedGCN_DGG) takes the same configuration and the same node, and gets back its own rows"""
         from .parallel import ShardedDGGConv
         why = self._fused_outside(x, in_adj, conv_weight)
         if why is not None:
             return self._fused_fallback(why)
+        logs = writer is not None and self.training
+        if logs:
+            self._refuse_captured_writer()
         N = x.shape[0]
         mlp_mode, wide_state, el_wide = getattr(self._scorer(), "fused", False), None, False
-        in_adj, cand, deg, _, _, _ = self._candidates(in_adj)
+        in_adj, cand, deg, prior, _, _ = self._candidates(in_adj)
         if cand is None:
             # (args.dgg_wide_rows is u-v-dist's: the edge-MLP scorers have args.dgg_allpairs_mlp_rows, and no CSR form on all pairs)
             if not mlp_mode and (self.__dict__.get("_ap_wide", {}).get("on") or self._allpairs_csr_plan(N) == "csr"):
@@ -779,7 +785,14 @@ class DGG_LearnableK_debug(nn.Module):
             Z, ahat = _FusedDGGMlpConvFn.apply(x, deg, layer, sc_static, *_sc_terms(mlp), *params)
         else:
             Z, ahat = _FusedDGGConvFn.apply(x, deg, layer, *params)       # (ops.ChunkCapacityError: a learned degree is NaN)
-        return self._fused_result(layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm, el_wide=el_wide)
+        res = self._fused_result(layer, Z, ahat, in_adj, cand, noise_mode, chunk_active, mlp_mode, want_norm, el_wide=el_wide)
+        if logs and res is not None:                          # (a discarded forward writes nothing: the separate modules log their own)
+            st = layer.saved
+            lay = st.get("layout")
+            lay = lay if (lay is not None and lay.wide) else None
+            fk = self._log_first_k(writer, epoch, dict(mode=layer.mode), st["w"], st["val"], lay, defer=True)
+            self._log_adj_stats(writer, epoch, self._stats_graph(in_adj, cand, deg, prior), st["idx"], st["w"], lay, st["k"], first_k=fk)
+        return res
 
     def _fused_outside(self, x, in_adj, conv_weight):
         """-> the reason this configuration is outside the fused layer, or None.  Which clause sends a forward to the separate modules
@@ -1050,14 +1063,84 @@ class DGG_LearnableK_debug(nn.Module):
         return rows == "chunked"
 
     @staticmethod
-    def _log_first_k(writer, epoch, cfg, w, val, lay=None):
-        """the two scalars the reference logs from inside the DGG (dgm.py:1259-1261); lay: on chunked rows"""
+    def _log_first_k(writer, epoch, cfg, w, val, lay=None, defer=False):
+        """the two scalars the reference logs from inside the DGG (dgm.py:1259-1261); lay: on chunked rows.  defer: nothing is written --
+        -> the two device scalars (std, mean), which _log_adj_stats(first_k=) writes from its own read-back"""
         if writer is None:
             return
         f = w.detach() if (cfg["mode"] == ops.MODE_K_ONLY or "fwd_mode" in cfg) else (w.detach() / val.clamp(min=1e-30))
         fs = f.sum(-1) if lay is None else torch.zeros(lay.rows, device=w.device).index_add_(0, lay.cnode.long(), f.sum(-1))
+        if defer:
+            return fs.std(), fs.mean()
         writer.add_scalar("values/first_k_std", fs.std(), epoch)
         writer.add_scalar("values/first_k_mean", fs.mean(), epoch)
+
+    _ADJ_STATS_TAGS = (("on_edge_mean", "on_mean"), ("on_edge_std", "on_std"), ("off_edge_mean", "off_mean"), ("off_edge_std", "off_std"),
+                       ("in_deg_mean", "in_deg_mean"), ("k_diff_mean", "k_diff_mean"), ("k_mean", "k_mean"))     # (dgm.py:1337-1348, in its order)
+
+    @staticmethod
+    def _refuse_captured_writer():
+        if _capturing():
+            raise RuntimeError("DGG_LearnableK_debug: a writer in training mode reads the logged scalars back from the device (one "
+                               "read-back per logged forward), which a hipGraph capture cannot do; capture the forward with writer=None")
+
+    @staticmethod
+    def _stats_graph(in_adj, cand, deg, prior):
+        """the graph train_stats/* compares the learned adjacency with -> (rowptr, col, values) in CSR, or the prior degrees alone.
+        Edge-list candidates: the in_adj the generator was given (GCN_DGG passes in_adj + I); AllPairs with a prior: the prior;
+        AllPairs without one has no stored values: its prior_degree [N] (in_deg_mean, k_diff_mean and k_mean only)."""
+        if cand is None:
+            return deg if prior is None else prior[:3]
+        return cand[0], cand[1], _cached("values_f32", in_adj, lambda: in_adj.coalesce().values().to(torch.float32).contiguous())
+
+    def _log_adj_stats(self, writer, epoch, graph_csr, idx, w, layout, k, first_k=None):
+        """train_stats/* of the reference (get_adj_diff_stats, dgm.py:1288, 1313-1350: how far the learned SOFT adjacency has moved from
+        the input graph, and the learned degree from the input degree) for a learned adjacency on the 64-rank list (idx / w [N,K]) or on
+        chunked rows (layout) against graph_csr (_stats_graph): ops.adj_diff_stats on the sparse data, ONE read-back of its ten
+        floats, seven add_scalar calls with Python floats.  Only with a writer in training mode -- the reference computes the numbers in
+        eval too and writes nothing there (dgm.py:1335).  graph_csr a degree vector (AllPairs without a prior): the three scalars that
+        need no stored value, from a float64 torch evaluation; the four on / off tags are skipped.
+        first_k = _log_first_k(defer=True)'s (std, mean): values/first_k_* are written first, as Python floats from the SAME read-back."""
+        if writer is None or not self.training:
+            return
+        self._refuse_captured_writer()
+        if torch.is_tensor(graph_csr):
+            dg, kd = graph_csr.detach().double(), k.detach().double()
+            names, out = ("in_deg_mean", "k_diff_mean", "k_mean"), torch.stack([dg.mean(), (kd - dg).mean(), kd.mean()])
+        else:
+            names, out = ops.ADJ_STATS_FIELDS, ops.adj_diff_stats((idx, w, layout), graph_csr, k)
+        if first_k is not None:                               # (float32 -> float64 is exact: the floats are the ones out.tolist() gives)
+            names, out = ("first_k_std", "first_k_mean") + tuple(names), torch.cat([torch.stack(first_k).double(), out.double()])
+        vals = dict(zip(names, out.tolist()))
+        if first_k is not None:
+            writer.add_scalar("values/first_k_std", vals["first_k_std"], epoch)
+            writer.add_scalar("values/first_k_mean", vals["first_k_mean"], epoch)
+        for tag, key in self._ADJ_STATS_TAGS:
+            if key in vals:
+                writer.add_scalar("train_stats/" + tag, vals[key], epoch)
+
+    def _log_adj_stats_csr(self, writer, epoch, a, w, k, deg):
+        """_log_adj_stats for the CSR form of select_top_k (_csr_soft_adjacency): the soft values w [E] are aligned with the candidate
+        pattern and so are the input values a [E] (None: AllPairs without a prior), so the statistics are elementwise -- a float64
+        TORCH evaluation (two-pass mean / unbiased std; a handful of elementwise launches and one read-back), not the kernel: this
+        form ranks every candidate of every row already, and no join is left to do.  deg [N]: the input degrees."""
+        if writer is None or not self.training:
+            return
+        self._refuse_captured_writer()
+        nan = float("nan")
+        dg, kd = deg.detach().double(), k.detach().double()
+        vals = [dg.mean(), (kd - dg).mean(), kd.mean()]
+        if a is not None:
+            d = a - w.detach()                                # (float32, as the reference subtracts)
+            for m in (a > 0, a == 0):
+                pop = d[m & (d != 0)].double()
+                n = pop.numel()
+                vals += [pop.mean() if n else dg.new_tensor(nan), pop.std() if n > 1 else dg.new_tensor(nan)]
+        vals = torch.stack(vals).tolist()
+        named = dict(zip(("in_deg_mean", "k_diff_mean", "k_mean", "on_mean", "on_std", "off_mean", "off_std"), vals))
+        for tag, key in self._ADJ_STATS_TAGS:
+            if key in named:
+                writer.add_scalar("train_stats/" + tag, named[key], epoch)
 
     def _track_overflow(self, k, ncand):
         over = k.detach() + 8.5 > float(self.ell_width)
@@ -1150,19 +1233,35 @@ class DGG_LearnableK_debug(nn.Module):
             st["on"] = bool((k.detach() + 8.5 > float(self.ell_width)).any().item())
         return st["on"]
 
-    def _csr_soft_adjacency(self, x, in_adj, k, noise_mode, G, seed, mode, pattern=None, deg=None, rows=None):
+    def _csr_soft_adjacency(self, x, in_adj, k, noise_mode, G, seed, mode, pattern=None, deg=None, rows=None, log=None):
         """select_top_k on the CSR pattern of in_adj (ops.CsrSoftkFn: rows of any width, exact for any learned degree): edge
         probabilities as in _scores_adjacency, then perturbation + rank + ramp per row.  pattern / deg given (all-pairs candidates):
         the complete pattern, no in_adj.
         rows = (r0, r1) (dgg_amd.distributed.ShardedGCN_DGG): rows [r0, r1) of in_adj only, k their learned degrees [r1 - r0]; x and the
         projection stay the whole graph's -> the CsrAdjacency of those rows (global columns, the bits of the whole graph's rows), whose
-        backward leaves the shard's share of every gradient."""
+        backward leaves the shard's share of every gradient.
+        log = (writer, epoch, _stats_graph's answer): train_stats/* of the soft values before any straight-through replacement
+        (_log_adj_stats_csr; the whole graph only)."""
         assert rows is None or (in_adj is not None and G is None and not self.hard), "a row shard: edge-list candidates, counter-based noise, soft output"
+        assert rows is None or log is None, "a row shard writes no scalars"
         p, pattern = self._edge_probs(x, in_adj, pattern, deg, rows)
         if rows is not None:
             w = ops.CsrSoftkRowsFn.apply(p, k, pattern[0], pattern[1], rows, x.shape[0], noise_mode, seed, mode)
             return CsrAdjacency(pattern[0], pattern[1], pattern[2], w, x.shape[0], k=k.detach(), row0=rows[0], n_rows=rows[1] - rows[0])
         w = ops.CsrSoftkFn.apply(p, k, pattern[0], pattern[1], noise_mode, G, seed, mode)
+        if log is not None and log[0] is not None and self.training:
+            graph, N_ = log[2], x.shape[0]
+            if torch.is_tensor(graph):                        # AllPairs without a prior: no stored values
+                a, dg = None, graph
+            elif in_adj is not None:                          # edge-list candidates: the pattern IS the graph's
+                a, dg = graph[2], csr_candidates(in_adj)[2]
+            else:                                             # the complete pattern against a prior: its values scattered over the pairs
+                erow = torch.repeat_interleave(torch.arange(N_, device=x.device), graph[0][1:] - graph[0][:-1])
+                ne = int(erow.shape[0])                       # (a prior without entries keeps one placeholder entry in col / val)
+                a = torch.zeros(N_ * N_, device=x.device).index_put_((erow * N_ + graph[1][:ne].long(),), graph[2][:ne])
+                cs = torch.cat([a.new_zeros(1, dtype=torch.float64), graph[2][:ne].double().cumsum(0)])
+                dg = cs[graph[0][1:]] - cs[graph[0][:-1]]
+            self._log_adj_stats_csr(log[0], log[1], a, w, k, dg)
         if self.hard and mode == ops.MODE_K_TIMES_EDGE_PROB:      # straight-through (see forward): ramp mask forward, soft gradient
             ramp = ops.CsrSoftkFn.apply(p.detach(), k.detach(), pattern[0], pattern[1], noise_mode, G, seed, ops.MODE_K_ONLY)
             w = (ramp - w).detach() + w
@@ -1411,6 +1510,8 @@ class DGG_LearnableK_debug(nn.Module):
             self._sym_switch()
         self._note_rsym(cfg, x.shape[0])
         self._log_first_k(writer, epoch, cfg, w, val)
+        # (straight-through dgg_hard: w is the ramp mask's forward value; the soft value dgm.py:1288 reads is score x ramp)
+        self._log_adj_stats(writer, epoch, cfg.get("stats_graph"), idx, w.detach() * val if "fwd_mode" in cfg else w, None, k)
         if literal:
             # reference dgm.py:1294-1311 to the letter: ones where the RANK of a column equals the column INDEX of a strong neighbour
             We, be = self.node_encode_for_edges[0].weight, self.node_encode_for_edges[0].bias
@@ -1454,9 +1555,14 @@ class DGG_LearnableK_debug(nn.Module):
             # not a function of the graph; args.dgg_hard_literal=True reproduces it (small graphs).
             cfg["fwd_mode"] = ops.MODE_HARD_ST
         xp_dual, k = self._learned_k(x, in_adj, cand, deg, prior, literal)
+        logs = writer is not None and self.training
+        if logs:                                     # train_stats/*: the graph the learned adjacency is compared with
+            self._refuse_captured_writer()
+            cfg["stats_graph"] = self._stats_graph(in_adj, cand, deg, prior)
+        log = (writer, epoch, cfg["stats_graph"]) if logs else None
         if cand is not None and not literal and self._wide_rows(in_adj, cand[0], k):
             # row form: rows wider than the ELL and learned degrees that may exceed it take the CSR form (no width limit)
-            return self._csr_soft_adjacency(x, in_adj, k, noise_mode, G, seed, cfg["mode"])
+            return self._csr_soft_adjacency(x, in_adj, k, noise_mode, G, seed, cfg["mode"], log=log)
         chunk_checked = False
         if cand is None and not literal and (self._allpairs_mlp_chunked() if ap_mlp else self._chunk_policy(noise_mode)) and not _capturing():
             # learned degrees beyond the 64-rank list: chunked rows, ceil(k_i + 8.5) + 1 ranks per row in chunks of 64 (same generator, same search)
@@ -1465,13 +1571,14 @@ class DGG_LearnableK_debug(nn.Module):
                 cfg["layout"] = lay
                 w, idx, val, rs = self._scorer_node(x, k, cfg, xp_dual, deg, prior, erow, avals)
                 self._log_first_k(writer, epoch, cfg, w, val, lay)
+                self._log_adj_stats(writer, epoch, cfg.get("stats_graph"), idx, w.detach() * val if "fwd_mode" in cfg else w, lay, k)
                 return EllAdjacency(idx, w, N, rs=rs, k=k.detach(), score=val, owner=self, layout=lay)
             chunk_checked = lay is not None
         if cand is None and not literal and not mlp and not chunk_checked and self._allpairs_wide(N, k):
             # learned degrees beyond the list on all-pairs candidates: every column ranked, CSR form (per-pair hash noise: the ranked
             # generators produce a row's noise in decreasing order for a search that stops early -- here nothing stops early)
             return self._csr_soft_adjacency(x, None, k, ops.hash_noise_mode(noise_mode), G, seed, cfg["mode"],
-                                            pattern=self._allpairs_pattern(N, x.device), deg=deg)
+                                            pattern=self._allpairs_pattern(N, x.device), deg=deg, log=log)
         out = self._scorer_node(x, k, cfg, xp_dual, deg, prior, erow, avals)
         return self._list_result(x, k, cfg, out, cand, chunk_checked, literal, writer, epoch)
 

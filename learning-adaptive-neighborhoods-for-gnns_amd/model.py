@@ -125,7 +125,11 @@ class GCN_DGG(nn.Module):
     DETACHED -- the reference returns the differentiable output of dgg_net (model.py:1290), but its scripts only log it
     (train_small_graphs.py:226-230, 268-270).  A loss term on the returned adjacency (a sparsity or degree regulariser) needs
     args.dgg_differentiable_adj = True (or args.dgg_fused_layer = False): the separate modules, whose unnorm_adj carries autograd
-    into the generator."""
+    into the generator.
+
+    A `writer` (any object with add_scalar(tag, float, step) and add_histogram) takes the separate modules, as it always has, and gets the
+    reference's scalars from them (values/first_k_*, train_stats/*); with args.dgg_writer_fused = True it stays on the fused layer,
+    which writes the same tags after its node (one device read-back per logged forward; not under a hipGraph capture)."""
 
     def __init__(self, nfeat=32, nlayers=None, nhidden=32, nclass=10, args=None, **kwargs):
         super().__init__()
@@ -136,6 +140,7 @@ class GCN_DGG(nn.Module):
         self.convs.append(self.conv2)
         self.dgg_adj_input = args.dgg_adj_input
         self.differentiable_adj = bool(getattr(args, "dgg_differentiable_adj", False))
+        self.writer_fused = bool(getattr(args, "dgg_writer_fused", False))
         self.dggs = nn.ModuleList([DGG_LearnableK_debug(in_dim=nfeat, latent_dim=nhidden, args=args)])
         self.params1 = list(self.conv1.parameters())
         self.params2 = list(self.conv2.parameters())
@@ -151,10 +156,10 @@ class GCN_DGG(nn.Module):
             fused = None
             if i < len(self.dggs):
                 src = in_adj if self.dgg_adj_input == "input_adj" else unnorm_adj
-                if writer is None and isinstance(conv, GCNConv) and isinstance(src, (torch.Tensor, AllPairs)) and x.is_cuda and not self.differentiable_adj:
+                if (writer is None or self.writer_fused) and isinstance(conv, GCNConv) and isinstance(src, (torch.Tensor, AllPairs)) and x.is_cuda and not self.differentiable_adj:
                     # generator + normalize_adj + this layer as one autograd node (one pass over x for the three projections and
                     # one for their weight gradients); None when the configuration is outside its coverage
-                    fused = self.dggs[i].forward_conv(x, src, conv.W, want_norm=True)
+                    fused = self.dggs[i].forward_conv(x, src, conv.W, want_norm=True, writer=writer, epoch=epoch)
                 if fused is not None:
                     x, unnorm_adj, norm_adj = fused
                 else:

@@ -222,6 +222,35 @@ def project_knet(x, layers, knet_seg, deg, mu_sd, W1, b1, Wmu, bmu, Wp, bp, forc
     return ys, k, u
 
 
+# layout of adj_diff_stats' result (include/dgg_hip_next.h, DGG_ADJ_STATS_*), and how often the wrapper has launched the kernel pair
+ADJ_STATS_FIELDS = ("on_n", "on_mean", "on_std", "off_n", "off_mean", "off_std", "in_deg_mean", "k_diff_mean", "k_diff_std", "k_mean")
+ADJ_STATS_CALLS = 0
+
+
+def adj_diff_stats(adjacency_arrays, graph_csr, k):
+    """get_adj_diff_stats (reference dgm.py:1313-1350) of a learned SOFT adjacency against the input graph, on sparse data
+    (dgg_adj_diff_stats) -> float32 [10] on the device in the order of ADJ_STATS_FIELDS, on the caller's stream, nothing read back.
+    adjacency_arrays: (idx int32, w float32) [rows,K] with K <= 64, or (idx, w, layout) for chunked rows [chunks,64] (a ChunkLayout;
+    one that is not `wide` is the 64-rank list); idx < 0 marks an empty slot.  graph_csr: (rowptr int64 [rows+1], col int32 ascending
+    within a row, aval float32, ...) as csr_pattern + the values / AllPairs.prior_csr() give it.  k [rows]: the learned degrees."""
+    global ADJ_STATS_CALLS
+    idx, w = _chk(adjacency_arrays[0], torch.int32), _chk(adjacency_arrays[1].detach())
+    lay = adjacency_arrays[2] if len(adjacency_arrays) > 2 else None
+    lay = lay if (lay is not None and lay.wide) else None
+    rowptr, col, aval = _chk(graph_csr[0], torch.int64), _chk(graph_csr[1], torch.int32), _chk(graph_csr[2].detach())
+    k = _chk(k.detach())
+    rows = k.shape[0]
+    assert idx.shape == w.shape and idx.ndim == 2 and rowptr.shape[0] == rows + 1 and col.shape[0] == aval.shape[0]
+    assert (lay.rows == rows and idx.shape[1] == 64) if lay is not None else idx.shape[0] == rows
+    out = torch.empty((len(ADJ_STATS_FIELDS),), device=k.device, dtype=torch.float32)
+    ws = torch.empty((12 * max((rows + 15) // 16, 1),), device=k.device, dtype=torch.float64)      # one record per 16 rows
+    ADJ_STATS_CALLS += 1
+    _lib.check(_lib.lib().dgg_adj_diff_stats(_ptr(idx), _ptr(w), rows, idx.shape[1], None if lay is None else _ptr(_chk(lay.cptr, torch.int32)),
+                                             0 if lay is None else idx.shape[0], _ptr(rowptr), _ptr(col), _ptr(aval), _ptr(k), _ptr(ws), _ptr(out),
+                                             _stream()), "adj_diff_stats")
+    return out
+
+
 def linear_bwd_multi(x, layers):
     """Weight (and bias) gradients of several layers that share the input x, in ONE pass over x:
     layers = [(W, y or None, dy, act, w_layout, need_db), ...] -> [(dW_s, db_s or None)].  The activation derivative of layer s

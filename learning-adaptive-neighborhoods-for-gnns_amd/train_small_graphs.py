@@ -9,7 +9,10 @@ as shipped: `--extra_edge_dim` defaults to 2 (the defaul
 features, dgm.py:1660-1662; the reference's default 0 shape-mismatches) and the script's `edge_index=` keyword is dropped
 for wrappers that reject it (reference GCN_DGG.forward raises TypeError on it).  Optimiser groups follow
 train_small_graphs.py:399-418 (GCNII / GCN / SAGE / GAT branches).
-Only the flags the model constructors / DGG read are kept (no tensorboard, no code snapshots).  `--checkpoint FILE` saves
+Only the flags the model constructors / DGG read are kept (no code snapshots).  `--log_dir DIR` gives the TRAINING forward a writer, as
+the reference script always does (train_small_graphs.py:378, 268-270): torch.utils.tensorboard.SummaryWriter where it imports, else
+dgg_amd.ScalarLog (one JSON line per scalar); the evaluation forward stays without one, and without the flag nothing changes.
+`--dgg_writer_fused true` keeps GCN_DGG's fused layer under the writer.  `--checkpoint FILE` saves
 the best-validation state in the reference's `save_checkpoint` layout (train_small_graphs.py:210-220: args, epoch,
 model_state_dict, optimizer_state_dict); `--resume FILE` loads `model_state_dict` as its `test_best` does (line 330) -- the
 modules keep the reference's state_dict keys, so files written by either side load in the other.
@@ -68,6 +71,8 @@ def build_parser():
     p.add_argument("--cache_dir", default=None, help="keep the parsed data set here (npz) and reuse it while the source files are unchanged")
     p.add_argument("--checkpoint", default=None, help="write the best-validation checkpoint here (reference save_checkpoint layout)")
     p.add_argument("--resume", default=None, help="load model_state_dict from a checkpoint before training")
+    p.add_argument("--log_dir", default=None, help="write the reference's training scalars here (values/first_k_*, train_stats/*, histograms)")
+    p.add_argument("--dgg_writer_fused", type=str2bool, default=False, help="GCN_DGG: a writer does not leave the fused layer")
     return p
 
 
@@ -86,6 +91,16 @@ def make_adjacency(d, noise_level, device):
         rows, cols, vals = D.add_noisy_edges(rows, cols, N, noise_level)
     ind = torch.from_numpy(np.stack([rows, cols]).astype(np.int64))
     return torch.sparse_coo_tensor(ind, torch.from_numpy(vals), (N, N)).coalesce().to(device)
+
+
+def make_writer(log_dir):
+    """the reference's SummaryWriter(log_dir) where tensorboard is installed, else the dependency-free dgg_amd.ScalarLog"""
+    try:
+        from torch.utils.tensorboard import SummaryWriter
+    except Exception:                      # (tensorboard missing, or one of ITS imports failing: any of them leaves the JSON log)
+        from .scalar_log import ScalarLog
+        return ScalarLog(log_dir)
+    return SummaryWriter(log_dir)
 
 
 def accuracy(out, y):
@@ -136,12 +151,13 @@ def main(argv=None):
         opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     if args.resume:
         model.load_state_dict(torch.load(args.resume, map_location=device)["model_state_dict"])
+    writer = make_writer(args.log_dir) if args.log_dir else None
     best, bad, t0 = float("inf"), 0, time.time()
     for epoch in range(args.epochs):
         model.train()
         opt.zero_grad()
         with ops.step_zero_pool(device, x.shape[0], 64, max(args.hidden, 64), list(model.parameters())):   # one fill for the step's accumulators
-            out = forward(model, x, adj, edge_index=edge_index, epoch=epoch, writer=None)
+            out = forward(model, x, adj, edge_index=edge_index, epoch=epoch, writer=writer)
             loss = F.nll_loss(out[idx["train_idx"]], y[idx["train_idx"]])
             loss.backward()
         # BEFORE the optimiser step: the learned k must have stayed inside the ELL width and the noise generator must have settled
@@ -165,6 +181,8 @@ def main(argv=None):
             bad += 1
         if bad == args.patience:
             break
+    if writer is not None:
+        writer.close()
     print("Train cost: {:.4f}s".format(time.time() - t0))
     return best
 
