@@ -1781,11 +1781,62 @@ int dgg_ell_conv_bwd_part(const float *G, const float *H, const float *ahat, int
     return dgg_check_launch("ell_conv_bwd_part");
 }
 
+}  // extern "C"
+
 // ---- payload partition (16-byte records carrying wa = w * rs_i^-1/2 and the score; no slot map) ---------------------------
-int dgg_partp_build_norm(const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows, int K, int64_t ncols,
-                         const float *rs_all, float *ahat, void *ws, void *stream);
-int dgg_partp_build_phase(const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows, int K, int64_t ncols,
-                          const float *rs_all, float *ahat, void *ws, int phase, void *stream);
+// Every entry below is a thin wrapper: 64-rank lists and chunked rows (rows wider than 64 ranks, dgg_chunk_layout: the block is the
+// [chunks,64] arrays, K = 64, and the node of every chunk comes along) share one implementation per step.
+static int refuse(int code, const char *entry, const char *why) {
+    char msg[384];
+    snprintf(msg, sizeof(msg), "%s: %s", entry, why);
+    return dgg_set_error(code, msg);
+}
+
+// The stages of the build, and the sets of them that the ABI's `phase` names.  The split exists so that a caller can run the sort
+// beside other work on another stream, or not at all:
+//   count  per-bucket counts of every workgroup; with rs_all also the table ainv [ncols] = rs_all^-1/2 -- alone, all that
+//          dgg_ell_spmm_norm_act_fwd reads
+//   fill   scan + fill: the records in bucket order and, given ahat, ahat [rows,K] complete
+//   sort   the per-bucket sort: records in node order + nodeptr, what the backward's column kernels read
+//   records only   rs_all WITHOUT ahat: ainv is filled, the fill pass writes the records alone -- no a_j gathers, no ahat stores (the
+//          aggregation normalises); without this flag rs_all and ahat go together
+// phase 0 = count + fill + sort, 1 = count + fill, 2 = sort, 3 = count, 4 / 5 = phases 1 / 0 records only (3..5: since ABI v6)
+enum : unsigned { PP_COUNT = 1, PP_FILL = 2, PP_SORT = 4, PP_RECORDS_ONLY = 8 };
+static unsigned pp_stages(int phase) {
+    switch (phase) {
+        case 0: return PP_COUNT | PP_FILL | PP_SORT;
+        case 1: return PP_COUNT | PP_FILL;
+        case 2: return PP_SORT;
+        case 3: return PP_COUNT;
+        case 4: return PP_COUNT | PP_FILL | PP_RECORDS_ONLY;
+        case 5: return PP_COUNT | PP_FILL | PP_SORT | PP_RECORDS_ONLY;
+        default: return 0;
+    }
+}
+
+// cnode != NULL: chunked rows (rs_rows is indexed through it, the sorted records carry the chunk's source node, no slot -> record map)
+template <int TT>
+static void pp_launch(unsigned stages, const PartP2 &p, const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows,
+                      int K, int64_t ncols, const float *rs_all, float *ahat, const int32_t *cnode, hipStream_t st) {
+    const int nb = (int)p.nb, nwg = (int)p.nwg, pbs = p.width;
+    if (stages & PP_COUNT)
+        hipLaunchKernelGGL(pp_count<TT>, dim3((unsigned)nwg), dim3(TT), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv);
+    if (stages & PP_FILL) {
+        hipLaunchKernelGGL(pp_scan, dim3((unsigned)((nb + 31) / 32)), dim3(1024), 0, st, p.T, nwg, nb, p.totals);
+        hipLaunchKernelGGL(pp_fill<TT>, dim3((unsigned)nwg), dim3(TT), (size_t)(2 * nb + 16) * 4, st, idx, w, val, rs_rows, rows, K, nb, p.rcp, p.T,
+                           p.totals, p.bstart, p.tmp, p.ainv, ahat, cnode);
+    }
+    if (!(stages & PP_SORT)) return;
+    if (cnode)
+        hipLaunchKernelGGL(pp_sort<true>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr,
+                           (int *)nullptr, nb, pbs, cnode);
+    else
+        hipLaunchKernelGGL(pp_sort<false>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr,
+                           pp_builds_map(rows) ? p.recpos : nullptr, nb, pbs, (const int32_t *)nullptr);
+}
+
+extern "C" {
+
 size_t dgg_partp_ws_bytes(int64_t rows, int K, int64_t ncols) {
     if (K > 64 || K < 1 || rows * 64 >= ((int64_t)1 << 31) || ncols < 1) return 0;          // 32-bit record ids
     PartP2 p;
@@ -1796,74 +1847,62 @@ size_t dgg_partp_ws_bytes(int64_t rows, int K, int64_t ncols) {
 
 // Partition the ACTIVE entries (idx >= 0, w != 0) of an ELL block by destination, records = (row*64 + r, j, w * rs_i^-1/2, val).
 // val [rows,K] = the scores (dgg_allpairs_topk / dgg_edgelist_topk), rs_rows [rows] = the row sums of the block's OWN rows.
+// `chunked`: the block is the [rows = chunks,64] arrays of chunked rows, rs_rows [nodes of the block] is indexed through cnode [chunks].
+// Checks in this order: the phase, the size and the workspace, the operands of the requested stages, alignment, the empty block.
+static int partp_build_impl(const char *entry, const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows, int K,
+                            int64_t ncols, const float *rs_all, float *ahat, const int32_t *cnode, bool chunked, void *ws, int phase,
+                            void *stream) {
+    const unsigned stages = pp_stages(phase);
+    if (!stages) return refuse(DGG_ERR_ARG, entry, "phase is 0 (all), 1 (count + fill), 2 (sort), 3 (count), 4 or 5 (1 or 0, records only)");
+    if (dgg_partp_ws_bytes(rows, K, ncols) == 0 || !ws) return refuse(DGG_ERR_UNSUPPORTED, entry, "unsupported size or NULL workspace");
+    const bool count_only = stages == PP_COUNT;                  // reads idx, w and rs_all, nothing else
+    uintptr_t aligned = reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w);
+    if (count_only) {
+        if (!rs_all || !idx || !w) return refuse(DGG_ERR_ARG, entry, "phase 3 (count) needs idx, w and rs_all");
+        if (chunked) aligned |= reinterpret_cast<uintptr_t>(ahat);                               // (as this entry always has)
+    } else {
+        // (the sort alone reads neither val nor rs_rows and is asked for them all the same: one rule for every phase but 3)
+        if (!val || !rs_rows || (chunked && !cnode))
+            return refuse(DGG_ERR_ARG, entry, chunked ? "the payload needs the scores, the row sums and the chunk nodes" : "the payload needs the scores and the row sums");
+        if ((stages & PP_RECORDS_ONLY) && (!rs_all || ahat)) return refuse(DGG_ERR_ARG, entry, "phases 4 and 5 (records only) take rs_all and no ahat");
+        if (!(stages & PP_RECORDS_ONLY) && (rs_all == nullptr) != (ahat == nullptr)) return refuse(DGG_ERR_ARG, entry, "rs_all and ahat go together");
+        aligned |= reinterpret_cast<uintptr_t>(val) | reinterpret_cast<uintptr_t>(ahat);
+    }
+    if (K == 64 && aligned % 16) return refuse(DGG_ERR_ARG, entry, "idx / w / val / ahat must be 16-byte aligned");
+    if (rows == 0) return 0;
+    PartP2 p;
+    partp2_layout(p, ws, rows, K, ncols);
+    hipStream_t st = (hipStream_t)stream;
+    switch (pp_threads()) {
+        case 256: pp_launch<256>(stages, p, idx, w, val, rs_rows, rows, K, ncols, rs_all, ahat, cnode, st); break;
+        case 512: pp_launch<512>(stages, p, idx, w, val, rs_rows, rows, K, ncols, rs_all, ahat, cnode, st); break;
+        default: pp_launch<1024>(stages, p, idx, w, val, rs_rows, rows, K, ncols, rs_all, ahat, cnode, st); break;
+    }
+    return dgg_check_launch(entry);
+}
+
 int dgg_partp_build(const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows, int K, int64_t ncols,
                     void *ws, void *stream) {
-    return dgg_partp_build_norm(idx, w, val, rs_rows, rows, K, ncols, nullptr, nullptr, ws, stream);
+    return partp_build_impl("partp_build", idx, w, val, rs_rows, rows, K, ncols, nullptr, nullptr, nullptr, false, ws, 0, stream);
 }
 
 // the same with normalize_adj fused: rs_all [ncols] (row sums of EVERY node) -> ahat [rows,K] = rs_i^-1/2 w rs_j^-1/2, the bits
 // of dgg_ell_normalize_fwd (entries outside the partition: 0)
 int dgg_partp_build_norm(const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows, int K, int64_t ncols,
                          const float *rs_all, float *ahat, void *ws, void *stream) {
-    return dgg_partp_build_phase(idx, w, val, rs_rows, rows, K, ncols, rs_all, ahat, ws, 0, stream);
+    return partp_build_impl("partp_build_norm", idx, w, val, rs_rows, rows, K, ncols, rs_all, ahat, nullptr, false, ws, 0, stream);
 }
 
-// the same in two parts, so that a caller can run the second beside other work on another stream: phase 1 = count + scan + fill
-// (ahat is complete, the records sit in bucket order), phase 2 = the per-bucket sort (records in node order + nodeptr: what the
-// backward's column kernels read; the forward aggregation does not need it); phase 0 = both.
-// Since ABI v6 (include/dgg_hip_next.h): phase 3 = the count pass alone (ainv [ncols] = rs_all^-1/2 and nothing else: all that
-// dgg_ell_spmm_norm_act_fwd reads); phases 4 / 5 = phases 1 / 0 with rs_all and ahat == NULL: ainv is filled, the fill pass writes the
-// records only -- no a_j gathers, no ahat stores (at phases 0..2 rs_all and ahat still go together)
+// the same, the stages named by `phase` (see pp_stages)
 int dgg_partp_build_phase(const int32_t *idx, const float *w, const float *val, const float *rs_rows, int64_t rows, int K, int64_t ncols,
                           const float *rs_all, float *ahat, void *ws, int phase, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (phase < 0 || phase > 5)
-        return dgg_set_error(DGG_ERR_ARG, "partp_build_phase: phase is 0 (all), 1 (count + fill), 2 (sort), 3 (count), 4 / 5 (1 / 0, records only)");
-    if (dgg_partp_ws_bytes(rows, K, ncols) == 0 || !ws) return dgg_set_error(DGG_ERR_UNSUPPORTED, "partp_build: unsupported size or NULL workspace");
-    if (phase == 3) {                                            // the count pass alone: ainv [ncols] for the normalising aggregation
-        if (!rs_all || !idx || !w) return dgg_set_error(DGG_ERR_ARG, "partp_build_phase: phase 3 (count) needs idx, w and rs_all");
-        if (K == 64 && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w)) % 16))
-            return dgg_set_error(DGG_ERR_ARG, "partp_build: idx / w must be 16-byte aligned");
-    } else {
-        if (!val || !rs_rows) return dgg_set_error(DGG_ERR_ARG, "partp_build: the payload needs the scores and the row sums");
-        // phases 4 / 5: rs_all WITHOUT ahat -- ainv is filled, the fill pass writes records only (the aggregation normalises)
-        if (phase >= 4 && (!rs_all || ahat)) return dgg_set_error(DGG_ERR_ARG, "partp_build_phase: phases 4 / 5 take rs_all and no ahat");
-        if (phase < 4 && (rs_all == nullptr) != (ahat == nullptr)) return dgg_set_error(DGG_ERR_ARG, "partp_build_norm: rs_all and ahat go together");
-        if (K == 64 && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(val) |
-                         reinterpret_cast<uintptr_t>(ahat)) % 16))
-            return dgg_set_error(DGG_ERR_ARG, "partp_build: idx / w / val / ahat must be 16-byte aligned");
-    }
-    if (rows == 0) return 0;
-    PartP2 p;
-    partp2_layout(p, ws, rows, K, ncols);
-    const int nb = (int)p.nb, nwg = (int)p.nwg, pbs = p.width;
-    if (phase == 2) {
-        hipLaunchKernelGGL(pp_sort<false>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr, pp_builds_map(rows) ? p.recpos : nullptr, nb, pbs, (const int32_t *)nullptr);
-        return dgg_check_launch("partp_build");
-    }
-    if (phase == 3) {
-        switch (pp_threads()) {
-            case 256: hipLaunchKernelGGL(pp_count<256>, dim3((unsigned)nwg), dim3(256), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
-            case 512: hipLaunchKernelGGL(pp_count<512>, dim3((unsigned)nwg), dim3(512), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
-            default: hipLaunchKernelGGL(pp_count<1024>, dim3((unsigned)nwg), dim3(1024), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
-        }
-        return dgg_check_launch("partp_build");
-    }
-#define DGG_PP_PASS(TT)                                                                                                      \
-    hipLaunchKernelGGL(pp_count<TT>, dim3((unsigned)nwg), dim3(TT), (size_t)nb * 4, st, idx, w, rows, K, nb, p.rcp, p.T, rs_all, ncols, \
-                       p.ainv);                                                                                              \
-    hipLaunchKernelGGL(pp_scan, dim3((unsigned)((nb + 31) / 32)), dim3(1024), 0, st, p.T, nwg, nb, p.totals);                \
-    hipLaunchKernelGGL(pp_fill<TT>, dim3((unsigned)nwg), dim3(TT), (size_t)(2 * nb + 16) * 4, st, idx, w, val, rs_rows, rows, K, nb, p.rcp, \
-                       p.T, p.totals, p.bstart, p.tmp, p.ainv, ahat)
-    switch (pp_threads()) {
-        case 256: DGG_PP_PASS(256); break;
-        case 512: DGG_PP_PASS(512); break;
-        default: DGG_PP_PASS(1024); break;
-    }
-#undef DGG_PP_PASS
-    if (phase == 1 || phase == 4) return dgg_check_launch("partp_build");
-    hipLaunchKernelGGL(pp_sort<false>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr, pp_builds_map(rows) ? p.recpos : nullptr, nb, pbs, (const int32_t *)nullptr);
-    return dgg_check_launch("partp_build");
+    return partp_build_impl("partp_build_phase", idx, w, val, rs_rows, rows, K, ncols, rs_all, ahat, nullptr, false, ws, phase, stream);
+}
+// ... and on the [chunks,64] arrays of chunked rows: rs_nodes [nodes of the block] is indexed through cnode [chunks]; the SORTED records
+// carry (chunk * 64 + entry, SOURCE NODE of the chunk, w rs_i^-1/2, score) -- the destination is implied by nodeptr
+int dgg_partp_build_chunked(const int32_t *idx, const float *w, const float *val, const float *rs_nodes, int64_t chunks, const int32_t *cnode,
+                            int64_t ncols, const float *rs_all, float *ahat, void *ws, int phase, void *stream) {
+    return partp_build_impl("partp_build_chunked", idx, w, val, rs_nodes, chunks, 64, ncols, rs_all, ahat, cnode, true, ws, phase, stream);
 }
 
 // 1 when dgg_partp_build leaves the slot -> record map for a block of `rows` rows (then dgg_ell_conv_bwd_partp / dgg_softk_edge_bwd_partp
@@ -1914,38 +1953,34 @@ static bool node_groups(int64_t nrec, int64_t ncols) {
 // dgg_ell_conv_bwd_part on a payload partition: ahat comes from the records; additionally dA_rec [rows*K] = dA in record order
 // (for dgg_softk_edge_bwd_partp).  dH [ncols,F] and da [ncols]: one plain store per destination node (no zero fill by the caller);
 // dA [rows,K]: written on the active entries only (see include/dgg_hip.h).
-int dgg_ell_conv_bwd_partp_ext(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
-                               const float *rs, const float *dA_ext, float *dA, float *dA_rec, float *dH, float *da, void *stream);
-int dgg_ell_conv_bwd_partp(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
-                           const float *rs, float *dA, float *dA_rec, float *dH, float *da, void *stream) {
-    return dgg_ell_conv_bwd_partp_ext(G, H, rows, K, F, partp_ws, ncols, rs, nullptr, dA, dA_rec, dH, da, stream);
-}
-// the same with an additional cotangent of the normalised adjacency from its other consumers (dA_ext [rows,K], nullable; entries
-// outside the partition are not read): dA / dA_rec / da then hold the totals
-int dgg_ell_conv_bwd_partp_ext(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
-                               const float *rs, const float *dA_ext, float *dA, float *dA_rec, float *dH, float *da, void *stream) {
+// `chunked`: a partition built by dgg_partp_build_chunked (rows = chunks, K = 64) -- G [nodes of the block, F] is read at the record's
+// source node; dA is required and the node kernel is always the wavefront-per-node one
+static int conv_bwd_partp_impl(const char *entry, bool chunked, const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws,
+                               int64_t ncols, const float *rs, const float *dA_ext, float *dA, float *dA_rec, float *dH, float *da,
+                               void *stream) {
     if ((F != 16 && F != 32 && F != 64 && F != 128) || (reinterpret_cast<uintptr_t>(G) % 16) || (reinterpret_cast<uintptr_t>(H) % 16) ||
         (reinterpret_cast<uintptr_t>(dH) % 16))
-        return dgg_set_error(DGG_ERR_UNSUPPORTED, "ell_conv_bwd_partp: feature width must be 16, 32, 64 or 128 (16-byte aligned rows)");
-    if (!rs || !partp_ws || !dA_rec || dgg_partp_ws_bytes(rows, K, ncols) == 0) return dgg_set_error(DGG_ERR_ARG, "ell_conv_bwd_partp: missing operand");
+        return refuse(DGG_ERR_UNSUPPORTED, entry, "feature width must be 16, 32, 64 or 128 (16-byte aligned rows)");
+    if (!rs || !partp_ws || !dA_rec || (chunked && !dA) || dgg_partp_ws_bytes(rows, K, ncols) == 0) return refuse(DGG_ERR_ARG, entry, "missing operand");
     if (rows == 0) return 0;
     PartP2 p;
     partp2_layout(p, const_cast<void *>(partp_ws), rows, K, ncols);
     hipStream_t st = (hipStream_t)stream;
-    const bool grouped = !dA_ext && node_groups(rows * K, ncols);
+    const bool grouped = !chunked && !dA_ext && node_groups(rows * K, ncols);
     const unsigned nmain = (unsigned)((ncols + 3) / 4);
     const bool split = node_split(ncols);                         // long nodes in appended workgroups (see conv_bwd_node)
     const dim3 gridn(split ? nmain + (unsigned)ncols : nmain);
+    const int wide = chunked ? 1 : 0;
 #define DGG_CONV_COLS_P(FF)                                                                                                \
     if (dA_ext)                                                                                                            \
         hipLaunchKernelGGL((conv_bwd_node<FF, true>), gridn, dim3(256), 0, st, G, H, K, ncols, p.nodeptr, p.recs,          \
-                           rs, dA, dA_rec, dH, da, dA_ext, split ? nmain : 0u);                                            \
+                           rs, dA, dA_rec, dH, da, dA_ext, split ? nmain : 0u, wide);                                      \
     else if (grouped)                                                                                                      \
         hipLaunchKernelGGL((conv_bwd_nodeg<FF, 4>), dim3((unsigned)((ncols + 4 * (256 / FF) - 1) / (4 * (256 / FF)))), dim3(256), 0, st, G, H, K, \
                            ncols, p.nodeptr, p.recs, rs, dA, dA_rec, dH, da);                                              \
     else                                                                                                                   \
         hipLaunchKernelGGL((conv_bwd_node<FF, false>), gridn, dim3(256), 0, st, G, H, K, ncols, p.nodeptr, p.recs,         \
-                           rs, dA, dA_rec, dH, da, (const float *)nullptr, split ? nmain : 0u)
+                           rs, dA, dA_rec, dH, da, (const float *)nullptr, split ? nmain : 0u, wide)
     switch (F) {
         case 16: DGG_CONV_COLS_P(16); break;
         case 32: DGG_CONV_COLS_P(32); break;
@@ -1953,217 +1988,124 @@ int dgg_ell_conv_bwd_partp_ext(const float *G, const float *H, int64_t rows, int
         default: DGG_CONV_COLS_P(128); break;
     }
 #undef DGG_CONV_COLS_P
-    return dgg_check_launch("ell_conv_bwd_partp");
+    return dgg_check_launch(entry);
 }
 
-int dgg_softk_edge_bwd_partp_phase(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
-                                   const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
-                                   int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
-                                   float *dxp, int out_act, int phase, void *stream);
+int dgg_ell_conv_bwd_partp(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
+                           const float *rs, float *dA, float *dA_rec, float *dH, float *da, void *stream) {
+    return conv_bwd_partp_impl("ell_conv_bwd_partp", false, G, H, rows, K, F, partp_ws, ncols, rs, nullptr, dA, dA_rec, dH, da, stream);
+}
+// the same with an additional cotangent of the normalised adjacency from its other consumers (dA_ext [rows,K], nullable; entries
+// outside the partition are not read): dA / dA_rec / da then hold the totals
+int dgg_ell_conv_bwd_partp_ext(const float *G, const float *H, int64_t rows, int K, int F, const void *partp_ws, int64_t ncols,
+                               const float *rs, const float *dA_ext, float *dA, float *dA_rec, float *dH, float *da, void *stream) {
+    return conv_bwd_partp_impl("ell_conv_bwd_partp_ext", false, G, H, rows, K, F, partp_ws, ncols, rs, dA_ext, dA, dA_rec, dH, da, stream);
+}
+// ... and on chunked rows: dA [chunks,64] (entries outside the partition are not written), dA_rec [chunks*64], dA_ext [chunks,64] (nullable)
+int dgg_ell_conv_bwd_partp_chunked(const float *G, const float *H, int64_t chunks, int F, const void *partp_ws, int64_t ncols, const float *rs,
+                                   const float *dA_ext, float *dA, float *dA_rec, float *dH, float *da, void *stream) {
+    return conv_bwd_partp_impl("ell_conv_bwd_partp_chunked", true, G, H, chunks, 64, F, partp_ws, ncols, rs, dA_ext, dA, dA_rec, dH, da, stream);
+}
+
 // dgg_softk_edge_bwd_part on a payload partition: the row kernel hands (a_i, d loss / d rs_i, k_i) per row to the column kernel
-// (rowinfo_ws: 4*rows floats), which recomputes d loss / d score from dA_rec in record order -- no slot map, no per-entry
-// coefficient hand-over.  dk [rows] written; dxp [ncols,h]: mode 0 stores every row (no zero fill by the caller), mode 1 only the
-// rows of the block (see include/dgg_hip.h).
-int dgg_softk_edge_bwd_partp(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
-                             const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
-                             int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
-                             float *dxp, int out_act, void *stream) {
-    return dgg_softk_edge_bwd_partp_phase(xp, rows, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, K, row0, t, perturb, mode, normalized,
-                                          partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, 0, stream);
-}
-
-// the same in two parts: phase 1 = the row kernel (dk and the rows' own side of dxp are complete: the k-net backward can start on
-// another stream), phase 2 = the per-destination kernel (dxp complete); phase 0 = both
-int dgg_softk_edge_bwd_partp_phase(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
-                                   const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
-                                   int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
-                                   float *dxp, int out_act, int phase, void *stream) {
-    return dgg_softk_edge_bwd_partp_tab(xp, rows, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, K, row0, t, perturb, mode, normalized, partp_ws,
-                                        ncols, rowinfo_ws, dk, dxp, out_act, phase, 0, stream);
-}
-// ... and with a_j of the row kernel from the partition's ainv table (ainv_table = 1: the partition was built with rs_all = rs)
-int dgg_softk_edge_bwd_partp_tab(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
-                                 const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
-                                 int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
-                                 float *dxp, int out_act, int phase, int ainv_table, void *stream) {
-    if (phase < 0 || phase > 2) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_phase: phase is 0 (all), 1 (rows) or 2 (nodes)");
-    if (mode != 0 && mode != 1) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: mode must be 0 (k_times) or 1 (k_only)");
+// (rowinfo_ws: 4 floats per row of the block), which recomputes d loss / d score from dA_rec in record order -- no slot map, no
+// per-entry coefficient hand-over.  dk [rows] written; dxp [ncols,h]: mode 0 stores every row (no zero fill by the caller), mode 1 only
+// the rows of the block (see include/dgg_hip.h).
+// phase 1 = the row kernel (dk and the rows' own side of dxp are complete: the k-net backward can start on another stream), phase 2 =
+// the per-destination kernel (dxp complete), phase 0 = both.  ainv_table = 1 (the partition was built with rs_all = rs): a_j of the
+// row kernel from the partition's ainv table.
+// `chunked`: `rows` NODES with chunks [cptr[i], cptr[i+1]) of idx / val / dA / ahat_rows [chunks,64] (K = 64, the partition's block has
+// `chunks` rows); cptr and dA are required (chunked rows have no slot -> record map), one wavefront per node walks its chunks and
+// the node kernel is always the wavefront-per-node one.  Lists: cptr is NULL and chunks = rows.
+static int edge_bwd_partp_impl(const char *entry, bool chunked, const float *xp, int64_t rows, const int32_t *cptr, int64_t chunks, int h,
+                               const int32_t *idx, const float *val, const float *k, const float *rs, const float *dA, const float *dA_rec,
+                               const float *da, const float *ahat_rows, int K, int64_t row0, float t, int perturb, int mode, int normalized,
+                               const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk, float *dxp, int out_act, int phase,
+                               int ainv_table, void *stream) {
+    if (phase < 0 || phase > 2) return refuse(DGG_ERR_ARG, entry, "phase is 0 (all), 1 (rows) or 2 (nodes)");
+    if (mode != 0 && mode != 1) return refuse(DGG_ERR_ARG, entry, "mode must be 0 (k_times) or 1 (k_only)");
     if (out_act != 0 && (out_act != 1 || mode != 0))             // (mode 1 launches no node kernel: nothing would apply the mask)
-        return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: out_act is 0 or 1 (LeakyReLU), mode 0 only");
-    if (!k || !dA_rec || !dk || !rowinfo_ws || (normalized && (!rs || !da))) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: missing operand");
+        return refuse(DGG_ERR_ARG, entry, "out_act is 0 or 1 (LeakyReLU), mode 0 only");
+    if (!k || !dA_rec || !dk || !rowinfo_ws || (normalized && (!rs || !da)) || (chunked && (!cptr || !dA)))
+        return refuse(DGG_ERR_ARG, entry, "missing operand");
     if (!dA && !(normalized && ahat_rows))       // (the slot -> record map covers the partition's entries; ahat_rows tells which those are)
-        return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: dA may be NULL only in the normalised form with ahat_rows");
+        return refuse(DGG_ERR_ARG, entry, "dA may be NULL only in the normalised form with ahat_rows");
     if (!dA && !pp_builds_map(rows))
-        return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: dA is NULL but the partition of a block this large carries no slot -> record "
-                                          "map (dgg_partp_has_map)");
-    if (ahat_rows && !normalized) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: ahat_rows is an operand of the normalised form");
-    if (!partp_ws || dgg_partp_ws_bytes(rows, K, ncols) == 0) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp: no partition");
+        return refuse(DGG_ERR_ARG, entry, "dA is NULL but the partition of a block this large carries no slot -> record map (dgg_partp_has_map)");
+    if (ahat_rows && !normalized) return refuse(DGG_ERR_ARG, entry, "ahat_rows is an operand of the normalised form");
+    if (!partp_ws || dgg_partp_ws_bytes(chunks, K, ncols) == 0) return refuse(DGG_ERR_ARG, entry, "no partition");
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     PartP2 p;
-    partp2_layout(p, const_cast<void *>(partp_ws), rows, K, ncols);
+    partp2_layout(p, const_cast<void *>(partp_ws), chunks, K, ncols);
     const SoftkArgs sk{k, rs, dA, da, mode, normalized, nullptr, dk, ahat_rows, reinterpret_cast<float4 *>(rowinfo_ws),
                        dA ? nullptr : p.recpos, dA_rec, (ainv_table && normalized) ? p.ainv : nullptr};
     const unsigned gr = (unsigned)((rows + 3) / 4);
-    const bool grouped = node_groups(rows * K, ncols);
+    const bool grouped = !chunked && node_groups(rows * K, ncols);
     const unsigned nmain = (unsigned)((ncols + 3) / 4);
     const bool split = node_split(ncols);
+    const int wide = chunked ? 1 : 0;
 #define DGG_EDGE_PARTP(HH)                                                                                                  \
-    if (phase != 2)                                                                                                          \
+    if (phase != 2 && chunked)                                                                                               \
+        hipLaunchKernelGGL((edge_bwd_rows_chunked<HH>), dim3(gr), dim3(256), 0, st, xp, rows, cptr, idx, val, row0, t, perturb, dxp, sk); \
+    else if (phase != 2)                                                                                                     \
         hipLaunchKernelGGL((edge_bwd_rows<HH, true, true>), dim3(gr), dim3(256), 0, st, xp, rows, idx, val, nullptr, K, row0, t, perturb, nullptr, \
                            nullptr, dxp, sk);                                                                                \
-    if (phase == 1) {                                                                                                        \
-    } else if (mode == 0 && grouped)                                                                                         \
+    if (phase == 1 || mode != 0) {                                                                                           \
+    } else if (grouped)                                                                                                      \
         hipLaunchKernelGGL((edge_bwd_nodeg<HH, 4>), dim3((unsigned)((ncols + 4 * (256 / HH) - 1) / (4 * (256 / HH)))), dim3(256), 0, st, xp, \
                            ncols, p.nodeptr, p.recs, dA_rec, reinterpret_cast<const float4 *>(rowinfo_ws), rs, normalized, row0, rows, t, \
                            perturb, dxp, out_act);                                                                           \
-    else if (mode == 0)                                                                                                      \
+    else                                                                                                                     \
         hipLaunchKernelGGL(edge_bwd_node<HH>, dim3(split ? nmain + (unsigned)ncols : nmain), dim3(256), 0, st, xp, ncols, p.nodeptr, p.recs, \
                            dA_rec, reinterpret_cast<const float4 *>(rowinfo_ws), rs, normalized, row0, rows, t, perturb, dxp, out_act,  \
-                           split ? nmain : 0u)
+                           split ? nmain : 0u, wide)
     switch (h) {
         case 16: DGG_EDGE_PARTP(16); break;
         case 32: DGG_EDGE_PARTP(32); break;
         case 64: DGG_EDGE_PARTP(64); break;
         case 128: DGG_EDGE_PARTP(128); break;
-        default: return dgg_set_error(DGG_ERR_UNSUPPORTED, "softk_edge_bwd_partp supports latent_dim in {16,32,64,128}");
+        default: return refuse(DGG_ERR_UNSUPPORTED, entry, "latent_dim must be 16, 32, 64 or 128");
     }
 #undef DGG_EDGE_PARTP
-    return dgg_check_launch("softk_edge_bwd_partp");
+    return dgg_check_launch(entry);
 }
 
-// ---- chunked rows (rows wider than 64 ranks, dgg_chunk_layout): the same three steps with the node of every chunk -----------------
-// dgg_partp_build_phase on the [chunks,64] arrays of chunked rows: rs_nodes [nodes of the block] is indexed through cnode [chunks];
-// the SORTED records carry (chunk * 64 + entry, SOURCE NODE of the chunk, w rs_i^-1/2, score) -- the destination is implied by nodeptr
-int dgg_partp_build_chunked(const int32_t *idx, const float *w, const float *val, const float *rs_nodes, int64_t chunks, const int32_t *cnode,
-                            int64_t ncols, const float *rs_all, float *ahat, void *ws, int phase, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const int K = 64;
-    // (phases 3, 4 / 5: as dgg_partp_build_phase -- the count pass alone; phases 1 / 0 with rs_all and no ahat, records only)
-    if (phase < 0 || phase > 5)
-        return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: phase is 0 (all), 1 (count + fill), 2 (sort), 3 (count), 4 / 5 (1 / 0, records only)");
-    if (dgg_partp_ws_bytes(chunks, K, ncols) == 0 || !ws) return dgg_set_error(DGG_ERR_UNSUPPORTED, "partp_build_chunked: unsupported size or NULL workspace");
-    if (phase == 3) {
-        if (!rs_all || !idx || !w) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: phase 3 (count) needs idx, w and rs_all");
-    } else {
-        if (!val || !rs_nodes || !cnode) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: the payload needs the scores, the row sums and the chunk nodes");
-        if (phase >= 4 && (!rs_all || ahat)) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: phases 4 / 5 take rs_all and no ahat");
-        if (phase < 4 && (rs_all == nullptr) != (ahat == nullptr)) return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: rs_all and ahat go together");
-    }
-    if ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | (phase == 3 ? 0 : reinterpret_cast<uintptr_t>(val)) | reinterpret_cast<uintptr_t>(ahat)) % 16)
-        return dgg_set_error(DGG_ERR_ARG, "partp_build_chunked: idx / w / val / ahat must be 16-byte aligned");
-    if (chunks == 0) return 0;
-    PartP2 p;
-    partp2_layout(p, ws, chunks, K, ncols);
-    const int nb = (int)p.nb, nwg = (int)p.nwg, pbs = p.width;
-    if (phase == 3) {
-        switch (pp_threads()) {
-            case 256: hipLaunchKernelGGL(pp_count<256>, dim3((unsigned)nwg), dim3(256), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
-            case 512: hipLaunchKernelGGL(pp_count<512>, dim3((unsigned)nwg), dim3(512), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
-            default: hipLaunchKernelGGL(pp_count<1024>, dim3((unsigned)nwg), dim3(1024), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, p.ainv); break;
-        }
-        return dgg_check_launch("partp_build_chunked");
-    }
-    if (phase != 2) {
-#define DGG_PP_PASS(TT)                                                                                                      \
-    hipLaunchKernelGGL(pp_count<TT>, dim3((unsigned)nwg), dim3(TT), (size_t)nb * 4, st, idx, w, chunks, K, nb, p.rcp, p.T, rs_all, ncols, \
-                       p.ainv);                                                                                              \
-    hipLaunchKernelGGL(pp_scan, dim3((unsigned)((nb + 31) / 32)), dim3(1024), 0, st, p.T, nwg, nb, p.totals);                \
-    hipLaunchKernelGGL(pp_fill<TT>, dim3((unsigned)nwg), dim3(TT), (size_t)(2 * nb + 16) * 4, st, idx, w, val, rs_nodes, chunks, K, nb, p.rcp, \
-                       p.T, p.totals, p.bstart, p.tmp, p.ainv, ahat, cnode)
-        switch (pp_threads()) {
-            case 256: DGG_PP_PASS(256); break;
-            case 512: DGG_PP_PASS(512); break;
-            default: DGG_PP_PASS(1024); break;
-        }
-#undef DGG_PP_PASS
-    }
-    if (phase != 1 && phase != 4)
-        hipLaunchKernelGGL(pp_sort<true>, dim3((unsigned)nb), dim3(PP_T), (size_t)(2 * pbs + 16) * 4, st, p.bstart, p.tmp, p.recs, p.nodeptr,
-                           (int *)nullptr, nb, pbs, cnode);
-    return dgg_check_launch("partp_build_chunked");
+int dgg_softk_edge_bwd_partp(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
+                             const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
+                             int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
+                             float *dxp, int out_act, void *stream) {
+    return edge_bwd_partp_impl("softk_edge_bwd_partp", false, xp, rows, nullptr, rows, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, K, row0, t,
+                               perturb, mode, normalized, partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, 0, 0, stream);
 }
-
-// dgg_ell_conv_bwd_partp_ext on a partition built by dgg_partp_build_chunked: G [nodes of the block, F] is read at the record's source
-// node; dA [chunks,64] (entries outside the partition are not written), dA_rec [chunks*64], dA_ext [chunks,64] (nullable)
-int dgg_ell_conv_bwd_partp_chunked(const float *G, const float *H, int64_t chunks, int F, const void *partp_ws, int64_t ncols, const float *rs,
-                                   const float *dA_ext, float *dA, float *dA_rec, float *dH, float *da, void *stream) {
-    const int K = 64;
-    if ((F != 16 && F != 32 && F != 64 && F != 128) || (reinterpret_cast<uintptr_t>(G) % 16) || (reinterpret_cast<uintptr_t>(H) % 16) ||
-        (reinterpret_cast<uintptr_t>(dH) % 16))
-        return dgg_set_error(DGG_ERR_UNSUPPORTED, "ell_conv_bwd_partp_chunked: feature width must be 16, 32, 64 or 128 (16-byte aligned rows)");
-    if (!rs || !partp_ws || !dA_rec || !dA || dgg_partp_ws_bytes(chunks, K, ncols) == 0) return dgg_set_error(DGG_ERR_ARG, "ell_conv_bwd_partp_chunked: missing operand");
-    if (chunks == 0) return 0;
-    PartP2 p;
-    partp2_layout(p, const_cast<void *>(partp_ws), chunks, K, ncols);
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned nmain = (unsigned)((ncols + 3) / 4);
-    const bool split = node_split(ncols);
-    const dim3 gridn(split ? nmain + (unsigned)ncols : nmain);
-#define DGG_CONV_COLS_C(FF)                                                                                                \
-    if (dA_ext)                                                                                                            \
-        hipLaunchKernelGGL((conv_bwd_node<FF, true>), gridn, dim3(256), 0, st, G, H, K, ncols, p.nodeptr, p.recs,          \
-                           rs, dA, dA_rec, dH, da, dA_ext, split ? nmain : 0u, 1);                                         \
-    else                                                                                                                   \
-        hipLaunchKernelGGL((conv_bwd_node<FF, false>), gridn, dim3(256), 0, st, G, H, K, ncols, p.nodeptr, p.recs,         \
-                           rs, dA, dA_rec, dH, da, (const float *)nullptr, split ? nmain : 0u, 1)
-    switch (F) {
-        case 16: DGG_CONV_COLS_C(16); break;
-        case 32: DGG_CONV_COLS_C(32); break;
-        case 64: DGG_CONV_COLS_C(64); break;
-        default: DGG_CONV_COLS_C(128); break;
-    }
-#undef DGG_CONV_COLS_C
-    return dgg_check_launch("ell_conv_bwd_partp_chunked");
+int dgg_softk_edge_bwd_partp_phase(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
+                                   const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
+                                   int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
+                                   float *dxp, int out_act, int phase, void *stream) {
+    return edge_bwd_partp_impl("softk_edge_bwd_partp_phase", false, xp, rows, nullptr, rows, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, K, row0, t,
+                               perturb, mode, normalized, partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, phase, 0, stream);
 }
-
-// dgg_softk_edge_bwd_partp_phase on chunked rows: `rows` NODES with chunks [cptr[i], cptr[i+1]) of idx / val / dA / ahat_rows [chunks,64];
-// k, dk [rows]; rowinfo_ws 4 * chunks floats; dA is required (no slot -> record map for chunked rows)
+int dgg_softk_edge_bwd_partp_tab(const float *xp, int64_t rows, int h, const int32_t *idx, const float *val, const float *k, const float *rs,
+                                 const float *dA, const float *dA_rec, const float *da, const float *ahat_rows, int K, int64_t row0, float t,
+                                 int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk,
+                                 float *dxp, int out_act, int phase, int ainv_table, void *stream) {
+    return edge_bwd_partp_impl("softk_edge_bwd_partp_tab", false, xp, rows, nullptr, rows, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, K, row0, t,
+                               perturb, mode, normalized, partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, phase, ainv_table, stream);
+}
 int dgg_softk_edge_bwd_partp_chunked(const float *xp, int64_t rows, const int32_t *cptr, int64_t chunks, int h, const int32_t *idx, const float *val,
                                      const float *k, const float *rs, const float *dA, const float *dA_rec, const float *da, const float *ahat_rows,
                                      int64_t row0, float t, int perturb, int mode, int normalized, const void *partp_ws, int64_t ncols,
                                      float *rowinfo_ws, float *dk, float *dxp, int out_act, int phase, void *stream) {
-    return dgg_softk_edge_bwd_partp_chunked_tab(xp, rows, cptr, chunks, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, row0, t, perturb, mode, normalized,
-                                                partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, phase, 0, stream);
+    return edge_bwd_partp_impl("softk_edge_bwd_partp_chunked", true, xp, rows, cptr, chunks, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, 64, row0, t,
+                               perturb, mode, normalized, partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, phase, 0, stream);
 }
 int dgg_softk_edge_bwd_partp_chunked_tab(const float *xp, int64_t rows, const int32_t *cptr, int64_t chunks, int h, const int32_t *idx,
                                          const float *val, const float *k, const float *rs, const float *dA, const float *dA_rec,
                                          const float *da, const float *ahat_rows, int64_t row0, float t, int perturb, int mode,
                                          int normalized, const void *partp_ws, int64_t ncols, float *rowinfo_ws, float *dk, float *dxp,
                                          int out_act, int phase, int ainv_table, void *stream) {
-    const int K = 64;
-    if (phase < 0 || phase > 2) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: phase is 0 (all), 1 (rows) or 2 (nodes)");
-    if (mode != 0 && mode != 1) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: mode must be 0 (k_times) or 1 (k_only)");
-    if (out_act != 0 && (out_act != 1 || mode != 0)) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: out_act is 0 or 1 (LeakyReLU), mode 0 only");
-    if (!k || !cptr || !dA || !dA_rec || !dk || !rowinfo_ws || (normalized && (!rs || !da)))
-        return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: missing operand");
-    if (ahat_rows && !normalized) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: ahat_rows is an operand of the normalised form");
-    if (!partp_ws || dgg_partp_ws_bytes(chunks, K, ncols) == 0) return dgg_set_error(DGG_ERR_ARG, "softk_edge_bwd_partp_chunked: no partition");
-    if (rows == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    PartP2 p;
-    partp2_layout(p, const_cast<void *>(partp_ws), chunks, K, ncols);
-    const SoftkArgs sk{k, rs, dA, da, mode, normalized, nullptr, dk, ahat_rows, reinterpret_cast<float4 *>(rowinfo_ws), nullptr, dA_rec,
-                       (ainv_table && normalized) ? p.ainv : nullptr};
-    const unsigned gr = (unsigned)((rows + 3) / 4);
-    const unsigned nmain = (unsigned)((ncols + 3) / 4);
-    const bool split = node_split(ncols);
-#define DGG_EDGE_PARTC(HH)                                                                                                   \
-    if (phase != 2)                                                                                                          \
-        hipLaunchKernelGGL((edge_bwd_rows_chunked<HH>), dim3(gr), dim3(256), 0, st, xp, rows, cptr, idx, val, row0, t, perturb, dxp, sk); \
-    if (phase != 1 && mode == 0)                                                                                             \
-        hipLaunchKernelGGL(edge_bwd_node<HH>, dim3(split ? nmain + (unsigned)ncols : nmain), dim3(256), 0, st, xp, ncols, p.nodeptr, p.recs, \
-                           dA_rec, reinterpret_cast<const float4 *>(rowinfo_ws), rs, normalized, row0, rows, t, perturb, dxp, out_act,  \
-                           split ? nmain : 0u, 1)
-    switch (h) {
-        case 16: DGG_EDGE_PARTC(16); break;
-        case 32: DGG_EDGE_PARTC(32); break;
-        case 64: DGG_EDGE_PARTC(64); break;
-        case 128: DGG_EDGE_PARTC(128); break;
-        default: return dgg_set_error(DGG_ERR_UNSUPPORTED, "softk_edge_bwd_partp_chunked supports latent_dim in {16,32,64,128}");
-    }
-#undef DGG_EDGE_PARTC
-    return dgg_check_launch("softk_edge_bwd_partp_chunked");
+    return edge_bwd_partp_impl("softk_edge_bwd_partp_chunked_tab", true, xp, rows, cptr, chunks, h, idx, val, k, rs, dA, dA_rec, da, ahat_rows, 64, row0,
+                               t, perturb, mode, normalized, partp_ws, ncols, rowinfo_ws, dk, dxp, out_act, phase, ainv_table, stream);
 }
 
 // dA [rows,64] (row-major; chunked rows: [chunks,64]) -> dA_rec [rows*64] in the record order of a built payload partition (K = 64)

@@ -1545,10 +1545,28 @@ def part_build(idx, w, ncols):
 class PartP:
     """payload partition (dgg_partp_build): workspace + the shape it was built for"""
 
-    def __init__(self, ws, rows, K, ncols, layout=None):
+    def __init__(self, ws, rows, K, ncols, layout=None, has_ainv=False):
         self.ws, self.rows, self.K, self.ncols = ws, rows, K, ncols
-        self.has_ainv = False                # built with rs_all: the workspace holds rs_j^-1/2 of every destination node
+        self.has_ainv = has_ainv             # built with rs_all: the workspace holds rs_j^-1/2 of every destination node
         self.layout = layout                 # ChunkLayout when the block is the [chunks,64] arrays of chunked rows (rows = chunks)
+        # the sort still to run, set by partp_build(phase=1): the operands (idx, w, val, rs_rows, rs_all, ahat) that partp_sort() hands to
+        # the build entry again (it checks them as at any phase; the sort reads none); None once sorted, or when there is nothing to sort
+        self.pending_sort = None
+
+    def skip_sort(self):
+        """the records stay in bucket order, unread (a forward that no backward follows): releases the operands kept for the sort"""
+        self.pending_sort = None
+
+    def _build(self, idx, w, val, rs_rows, rs_all, ahat, cphase, what):
+        """the build entry for this partition's form, lists or chunked rows, at the C phase `cphase`"""
+        L = _lib.lib()
+        if self.layout is not None:
+            rc = L.dgg_partp_build_chunked(_ptr(idx), _ptr(w), _ptr(val), _ptr(rs_rows), self.rows, _ptr(self.layout.cnode), self.ncols,
+                                           _ptr(rs_all), _ptr(ahat), _ptr(self.ws), cphase, _stream())
+        else:
+            rc = L.dgg_partp_build_phase(_ptr(idx), _ptr(w), _ptr(val), _ptr(rs_rows), self.rows, self.K, self.ncols, _ptr(rs_all), _ptr(ahat),
+                                         _ptr(self.ws), cphase, _stream())
+        _lib.check(rc, what)
 
 
 def partp_records(partp):
@@ -1578,62 +1596,29 @@ def partp_build(idx, w, val, rs_rows, ncols, rs_all=None, phase=0, layout=None, 
     if nbytes == 0:
         return None
     ws = torch.empty((nbytes,), device=idx.device, dtype=torch.uint8)
-    if not want_ahat:
+    wide = layout is not None and layout.wide
+    assert not wide or (K == 64 and N == layout.chunks and rs_rows.shape[0] == layout.rows)
+    if want_ahat:
+        assert rs_all is not None or wide or phase == 0
+        cphase = int(phase)
+    else:                                        # records only: the C entries' phases 5 and 4 are phases 0 and 1 with rs_all and no ahat
         assert rs_all is not None and phase in (0, 1, 3), "want_ahat=False: rs_all is required; phase 0, 1 or 3 (count only)"
-        wide = layout is not None and layout.wide
-        assert not wide or (K == 64 and N == layout.chunks and rs_rows.shape[0] == layout.rows)
-        cphase = {0: 5, 1: 4, 3: 3}[phase]          # (the C entries' phases 5 / 4: phases 0 / 1 with rs_all and no ahat)
-        pe = _probe_begin()
-        if wide:
-            _lib.check(_lib.lib().dgg_partp_build_chunked(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, _ptr(layout.cnode), ncols,
-                                                          _ptr(_chk(rs_all)), None, _ptr(ws), cphase, _stream()), "partp_build_chunked")
-        else:
-            _lib.check(_lib.lib().dgg_partp_build_phase(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, K, ncols,
-                                                        _ptr(_chk(rs_all)), None, _ptr(ws), cphase, _stream()), "partp_build_phase")
-        _probe_end("pp_count" if phase == 3 else "pp_fill", pe)
-        part = PartP(ws, N, K, ncols, layout if wide else None)
-        part.has_ainv = True
-        part.args = (idx, w, val, rs_rows, rs_all, None) if phase == 1 else None
-        return part, None
-    if layout is not None and layout.wide:
-        assert K == 64 and N == layout.chunks and rs_rows.shape[0] == layout.rows
-        ahat = torch.empty((N, K), device=idx.device, dtype=torch.float32) if rs_all is not None else None
-        _lib.check(_lib.lib().dgg_partp_build_chunked(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, _ptr(layout.cnode), ncols,
-                                                      _ptr(None if rs_all is None else _chk(rs_all)), _ptr(ahat), _ptr(ws), int(phase), _stream()),
-                   "partp_build_chunked")
-        part = PartP(ws, N, K, ncols, layout)
-        part.has_ainv = rs_all is not None
-        part.args = (idx, w, val, rs_rows, rs_all, ahat) if phase == 1 else None
-        return part if rs_all is None else (part, ahat)
-    if rs_all is None:
-        assert phase == 0
-        _lib.check(_lib.lib().dgg_partp_build(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, K, ncols, _ptr(ws), _stream()),
-                   "partp_build")
-        return PartP(ws, N, K, ncols)
-    ahat = torch.empty((N, K), device=idx.device, dtype=torch.float32)
-    _lib.check(_lib.lib().dgg_partp_build_phase(_ptr(idx), _ptr(_chk(w)), _ptr(_chk(val)), _ptr(_chk(rs_rows)), N, K, ncols, _ptr(_chk(rs_all)),
-                                                _ptr(ahat), _ptr(ws), int(phase), _stream()), "partp_build_norm")
-    part = PartP(ws, N, K, ncols)
-    part.has_ainv = True
-    part.args = (idx, w, val, rs_rows, rs_all, ahat) if phase == 1 else None
-    return part, ahat
+        cphase = 3 if phase == 3 else 5 - phase
+    ahat = torch.empty((N, K), device=idx.device, dtype=torch.float32) if want_ahat and rs_all is not None else None
+    part = PartP(ws, N, K, ncols, layout if wide else None, has_ainv=rs_all is not None)
+    pe = _probe_begin()
+    part._build(idx, _chk(w), _chk(val), _chk(rs_rows), None if rs_all is None else _chk(rs_all), ahat, cphase, "partp_build")
+    _probe_end("pp_count" if phase == 3 else "pp_fill", pe)
+    if phase == 1:                               # (without ahat the entry takes no rs_all at phase 2: they go together there)
+        part.pending_sort = (idx, w, val, rs_rows, rs_all if ahat is not None else None, ahat)
+    return part if rs_all is None else (part, ahat)
 
 
 def partp_sort(part):
     """second part of partp_build(phase=1): the per-bucket sort, on the CURRENT stream"""
-    idx, w, val, rs_rows, rs_all, ahat = part.args
-    if ahat is None:                         # (built with want_ahat=False; the sort reads neither)
-        rs_all = None
     pe = _probe_begin()
-    if part.layout is not None:
-        _lib.check(_lib.lib().dgg_partp_build_chunked(_ptr(idx), _ptr(w), _ptr(val), _ptr(rs_rows), part.rows, _ptr(part.layout.cnode), part.ncols,
-                                                      _ptr(rs_all), _ptr(ahat), _ptr(part.ws), 2, _stream()), "partp_sort")
-        part.args = None
-        _probe_end("pp_sort", pe)
-        return
-    _lib.check(_lib.lib().dgg_partp_build_phase(_ptr(idx), _ptr(w), _ptr(val), _ptr(rs_rows), part.rows, part.K, part.ncols, _ptr(rs_all),
-                                                _ptr(ahat), _ptr(part.ws), 2, _stream()), "partp_sort")
-    part.args = None
+    part._build(*part.pending_sort, 2, "partp_sort")
+    part.pending_sort = None
     _probe_end("pp_sort", pe)
 
 
@@ -1671,14 +1656,12 @@ def conv_bwd_cols_p(idx, H, G, partp, rs, zero_dA=True, dA_ext=None, want_dA=Tru
     if dA_ext is not None:
         dA_ext = _chk(dA_ext.contiguous())
         assert tuple(dA_ext.shape) == (N, K)
+    tail = (_ptr(partp.ws), ncols, _ptr(_chk(rs)), _ptr(dA_ext), _ptr(dA), _ptr(dA_rec), _ptr(dH), _ptr(da), _stream())
     if partp.layout is not None:                 # chunked rows: G [layout.rows, F] is read at the source node of a record's chunk
         assert want_dA and G.shape[0] == partp.layout.rows
-        _lib.check(_lib.lib().dgg_ell_conv_bwd_partp_chunked(_ptr(G), _ptr(H), N, F, _ptr(partp.ws), ncols, _ptr(_chk(rs)), _ptr(dA_ext), _ptr(dA),
-                                                             _ptr(dA_rec), _ptr(dH), _ptr(da), _stream()), "ell_conv_bwd_partp_chunked")
-        _probe_end("conv_bwd", pe)
-        return dA, dA_rec, dH, da
-    _lib.check(_lib.lib().dgg_ell_conv_bwd_partp_ext(_ptr(G), _ptr(H), N, K, F, _ptr(partp.ws), ncols, _ptr(_chk(rs)), _ptr(dA_ext), _ptr(dA),
-                                                     _ptr(dA_rec), _ptr(dH), _ptr(da), _stream()), "ell_conv_bwd_partp")
+        _lib.check(_lib.lib().dgg_ell_conv_bwd_partp_chunked(_ptr(G), _ptr(H), N, F, *tail), "ell_conv_bwd_partp_chunked")
+    else:
+        _lib.check(_lib.lib().dgg_ell_conv_bwd_partp_ext(_ptr(G), _ptr(H), N, K, F, *tail), "ell_conv_bwd_partp")
     _probe_end("conv_bwd", pe)
     return dA, dA_rec, dH, da
 
@@ -1709,20 +1692,15 @@ def softk_edge_bwd_p(xp, idx, val, k, dA, dA_rec, rs, da, row0, t, perturb, mode
         rowinfo = torch.empty((N, 4), device=xp.device, dtype=torch.float32)
         dk = torch.empty((nrows,), device=xp.device, dtype=torch.float32)
     pe = _probe_begin()
+    mid = (h, _ptr(idx), _ptr(_chk(val)), _ptr(_chk(k)), _ptr(rs), _ptr(None if dA is None else _chk(dA)), _ptr(dA_rec), _ptr(da),
+           _ptr(None if ahat_rows is None else _chk(ahat_rows)))
+    tail = (row0, t, int(perturb), mode, int(normalized), _ptr(partp.ws), Ng, _ptr(rowinfo), _ptr(dk), _ptr(dxp), int(out_act), int(phase), tab,
+            _stream())
     if lay is not None:                          # chunked rows: one wavefront per node walks its chunks; rowinfo per chunk
         assert dA is not None and K == 64
-        _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_chunked_tab(_ptr(xp), nrows, _ptr(lay.cptr), N, h, _ptr(idx), _ptr(_chk(val)), _ptr(_chk(k)), _ptr(rs),
-                                                                   _ptr(_chk(dA)), _ptr(dA_rec), _ptr(da), _ptr(None if ahat_rows is None else _chk(ahat_rows)),
-                                                                   row0, t, int(perturb), mode, int(normalized), _ptr(partp.ws), Ng, _ptr(rowinfo), _ptr(dk),
-                                                                   _ptr(dxp), int(out_act), int(phase), tab, _stream()), "softk_edge_bwd_partp_chunked")
-        _probe_end("edge_bwd" if phase == 0 else ("edge_bwd_rows" if phase == 1 else "edge_bwd_node"), pe)
-        if phase == 1:
-            return dxp, dk, (dxp, dk, rowinfo)
-        return dxp, dk
-    _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_tab(_ptr(xp), N, h, _ptr(idx), _ptr(_chk(val)), _ptr(_chk(k)), _ptr(rs), _ptr(None if dA is None else _chk(dA)),
-                                                       _ptr(dA_rec), _ptr(da), _ptr(None if ahat_rows is None else _chk(ahat_rows)), K, row0, t,
-                                                       int(perturb), mode, int(normalized), _ptr(partp.ws), Ng, _ptr(rowinfo), _ptr(dk),
-                                                       _ptr(dxp), int(out_act), int(phase), tab, _stream()), "softk_edge_bwd_partp")
+        _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_chunked_tab(_ptr(xp), nrows, _ptr(lay.cptr), N, *mid, *tail), "softk_edge_bwd_partp_chunked")
+    else:
+        _lib.check(_lib.lib().dgg_softk_edge_bwd_partp_tab(_ptr(xp), N, *mid, K, *tail), "softk_edge_bwd_partp")
     _probe_end("edge_bwd" if phase == 0 else ("edge_bwd_rows" if phase == 1 else "edge_bwd_node"), pe)
     if phase == 1:
         return dxp, dk, (dxp, dk, rowinfo)

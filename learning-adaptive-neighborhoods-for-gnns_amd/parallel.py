@@ -739,8 +739,7 @@ class ShardedDGGConv:
         normalize_adj fused into its fill pass -- when the namespace offers it and covers the shape), else part (index form), ahat,
         partp_sorted (False: want_backward was off and the sort was not launched), side_join (the sort runs on the side stream).
         With norm_in_spmm, where the namespace normalises inside the aggregation (spmm_norm_fwd; 64-rank lists or chunked rows, conv
-        width 16 / 32 / 64) the fill pass writes records only and ahat stays None for forward() to take from spmm_norm_fwd; with
-        want_backward off only the partition's count pass runs (the rs_j^-1/2 table).  DGG_NORM_IN_SPMM=0: ahat from the fill pass."""
+        width 16 / 32 / 64), ahat stays None for forward() to take from spmm_norm_fwd.  DGG_NORM_IN_SPMM=0: ahat from the fill pass."""
         kern, rs, lay = self.kern, s["rs"], s["layout"]
         use_p = s["xp"].shape[1] in KERNEL_WIDTHS and s["H_loc"].shape[1] in KERNEL_WIDTHS and self.mode in (0, 1)
         use_n = use_p and self.norm_in_spmm and s["idx"].shape[1] == 64 and s["H_loc"].shape[1] in (16, 32, 64)
@@ -750,19 +749,18 @@ class ShardedDGGConv:
         # leave it running on the side stream with nothing ever joining it)
         nobwd = use_p and not self.want_backward
         lkw = {} if lay is None else {"layout": lay}
-        got = None
-        if use_n:
-            got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, phase=3 if nobwd else (1 if ov else 0), want_ahat=False, **lkw)
-        elif use_p and (ov or nobwd):
-            got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, phase=1, **lkw)
-        elif use_p:
-            got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, **lkw)
+        # two independent choices.  Who normalises: the fill pass (ahat comes back) or the aggregation (records only).  Which stages:
+        # all three (0); count + fill (1: the sort runs on the side stream, or never -- the fill pass must still write ahat); the
+        # count pass alone (3: no backward follows and the aggregation normalises from the rs_j^-1/2 table)
+        want_ahat = not use_n
+        stages = 3 if (use_n and nobwd) else (1 if (ov or nobwd) else 0)
+        got = kern.partp_build(s["idx"], s["w"], s["val"], rs_local, self.N, rs, phase=stages, want_ahat=want_ahat, **lkw) if use_p else None
         assert lay is None or use_p, "chunked rows run on the payload partition (latent / conv widths 16, 32, 64, 128; soft modes)"
         s["partp"], s["ahat"] = got if got is not None else (None, None)
         s["side_join"] = False
         s["partp_sorted"] = not (nobwd and got is not None)
         if nobwd and got is not None:
-            s["partp"].args = None                  # (phase 1 only: ahat is complete, the records stay in bucket order, unread)
+            s["partp"].skip_sort()                  # (the records, if filled at all, stay in bucket order, unread)
         elif ov and got is not None:                # the sort runs beside the aggregation; the backward joins before its first column kernel
             main, side = torch.cuda.current_stream(), self._side_stream()
             side.wait_stream(main)

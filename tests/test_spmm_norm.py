@@ -180,6 +180,49 @@ def test_spare_chunks_of_a_fixed_capacity_get_zero_ahat(dev):
     assert torch.equal(ahat_n, ahat_o) and torch.equal(Y_n, Y_o) and bool((ahat_n[lay.chunks:] == 0).all())
 
 
+@pytest.mark.parametrize("form", ["list", "chunked"])
+def test_every_way_to_build_the_partition_gives_the_same_partition(dev, form):
+    """partp_build in every supported (phase, want_ahat), phase 1 finished by partp_sort: one nodeptr, one set of slot-ordered records,
+    one ahat; and the count-only partition (phase 3) normalises inside the aggregation to the bits of the records-only one"""
+    from dgg_amd import ops
+    if form == "chunked":
+        nodes, ncols = 91, 300
+        k, lay, hi, hw, hv, hrs, idx, w, val, rs_all = chunked_block(dev, ops, nodes, ncols, 5)
+        kw = {"layout": lay}
+    else:
+        nodes, ncols = 259, 300
+        idx, w, val, rs_all = to_dev(dev, *make_block(nodes, ncols, 0, 11))
+        kw = {}
+    rs_rows = rs_all[:nodes].contiguous()
+    parts, ahats = {}, {}
+    for phase, want_ahat in ((0, True), (1, True), (0, False), (1, False), (3, False)):
+        part, ahat = ops.partp_build(idx, w, val, rs_rows, ncols, rs_all, phase=phase, want_ahat=want_ahat, **kw)
+        assert part.has_ainv and (ahat is not None) == want_ahat
+        if phase == 1:
+            ops.partp_sort(part)
+        parts[phase, want_ahat] = part
+        if want_ahat:
+            ahats[phase, want_ahat] = ahat
+    if form == "list":
+        parts["plain"] = ops.partp_build(idx, w, val, rs_rows, ncols)
+        assert isinstance(parts["plain"], ops.PartP) and not parts["plain"].has_ainv
+    torch.cuda.synchronize()
+    count_only = parts.pop((3, False))           # (never filled: it has no records to compare)
+    nodeptr0, rec0 = sorted_records(ops, parts[0, True])
+    assert rec0.shape[0] == int(((idx >= 0) & (w != 0)).sum())
+    for how, part in parts.items():
+        nodeptr, rec = sorted_records(ops, part)
+        assert np.array_equal(nodeptr, nodeptr0), f"{how}: nodeptr differs"
+        assert np.array_equal(rec, rec0), f"{how}: records differ"
+    assert torch.equal(ahats[1, True], ahats[0, True]), "ahat of phase 1 differs from phase 0's"
+    H = torch.randn(ncols, 32, generator=torch.Generator().manual_seed(3)).to(dev)
+    Y_c, ahat_c = ops.spmm_norm_fwd(idx, w, rs_rows, count_only, H, ops.ACT_RELU, **kw)
+    Y_r, ahat_r = ops.spmm_norm_fwd(idx, w, rs_rows, parts[0, False], H, ops.ACT_RELU, **kw)
+    torch.cuda.synchronize()
+    assert torch.equal(Y_c, Y_r) and torch.equal(ahat_c, ahat_r), "the count-only partition normalises differently"
+    assert torch.equal(ahat_r, ahats[0, True]), "ahat of the aggregation differs from the fill pass's"
+
+
 @pytest.mark.parametrize("h", [16, 64, 128])
 @pytest.mark.parametrize("form", ["list", "shard", "chunked"])
 def test_row_kernel_with_the_table_equals_the_expression(dev, h, form):
