@@ -6,10 +6,12 @@ Public surface mirrors the reference's modules:
     dgg_amd.model.{GCNConv, GraphConvolution, DenseGraphConvolution, GCN_DGG, GCN_DGG_00, GCNII_DGG, GCNIIppi_DGG}  (model.py)
     dgg_amd.distributed.{ShardedGCN_DGG, global_nll_loss}                    (GCN_DGG row-sharded across GPUs)
 plus the containers `AllPairs` / `EllAdjacency` / `CsrAdjacency`, the raw kernel wrappers in `dgg_amd.ops` and `ScalarLog`, a
-dependency-free writer for the models' `writer=` argument.
+dependency-free writer for the models' `writer=` argument, and `adjacency_mse_loss`, the reference's supervision of the learned adjacency
+(train_reddit.py:236-251) on sparse rows (target: `dgg_amd.data.remove_interclass_edges`).
 """
 from . import _lib, ops  # noqa: F401
-from .adjacency import AllPairs, CsrAdjacency, EllAdjacency, csr_candidates, csr_pattern, ell_from_dense  # noqa: F401
+from .adjacency import (AllPairs, CsrAdjacency, EllAdjacency, adjacency_mse_loss, csr_candidates, csr_pattern,  # noqa: F401
+                        ell_from_dense)
 from .dgm import (DGG, DGG_Ablations, DGG_LearnableK_debug, DGG_LearnableK_SDD, DGG_StraightThrough,  # noqa: F401
                   LearnableKEncoder)
 from .model import (DenseGraphConv, DenseGraphConvolution, GAT_DGG_00, GAT_DGG_Ablations, GATConv_DGG, GCN_DGG, GCN_DGG_00,  # noqa: F401

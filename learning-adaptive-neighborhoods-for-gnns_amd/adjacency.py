@@ -267,3 +267,45 @@ def csr_candidates(in_adj):
         deg = (cs[rowptr[1:]] - cs[rowptr[:-1]]).float()
         return rowptr, col, deg
     return _cached("candidates", in_adj, make)
+
+
+def _target_csr(target):
+    """the supervision target as (rowptr int64, col int32, values float32): a CsrAdjacency's own arrays, or a sparse COO tensor through
+    csr_pattern and its cache (the same object every step is converted once)"""
+    if isinstance(target, CsrAdjacency):
+        if target.shape[0] != target.shape[1]:
+            raise NotImplementedError("adjacency_mse_loss: the target is a row shard; the loss is taken on the whole graph only")
+        return target.rowptr, target.col, target.values().detach().to(torch.float32), target.shape
+    if not (torch.is_tensor(target) and target.is_sparse):
+        raise TypeError(f"adjacency_mse_loss: target must be a sparse COO tensor or a CsrAdjacency, got {type(target).__name__}")
+    rowptr, col, _ = csr_pattern(target)
+    gval = _cached("values_f32", target, lambda: target.coalesce().values().detach().to(torch.float32).contiguous())
+    return rowptr, col, gval, tuple(target.shape)
+
+
+def adjacency_mse_loss(out_adj, target, reduction="mean"):
+    """F.mse_loss(out_adj.to_dense(), target.to_dense().float(), reduction=reduction) without either dense operand: the reference's
+    supervision of the learned adjacency (train_reddit.py:236-251, `loss_2`), at any N.
+    out_adj: the EllAdjacency (64-rank list or chunked rows) or CsrAdjacency of the WHOLE graph that a generator returned; a row shard
+    raises NotImplementedError.  target: a sparse COO tensor [N,N] (coalesced and converted once per tensor object; integer or bool
+    values are cast to float32) or a CsrAdjacency.  -> 0-dim float32 tensor on out_adj's device, differentiable with respect to
+    out_adj.values() (one kernel pair; the backward is an elementwise product)."""
+    if not isinstance(out_adj, (EllAdjacency, CsrAdjacency)):
+        raise TypeError(f"adjacency_mse_loss: out_adj must be an EllAdjacency or a CsrAdjacency, got {type(out_adj).__name__}")
+    if reduction not in ops.ADJ_LOSS_REDUCTIONS:
+        raise ValueError(f"adjacency_mse_loss: reduction must be 'mean' or 'sum', got {reduction!r}")
+    if out_adj.shape[0] != out_adj.shape[1]:
+        raise NotImplementedError(f"adjacency_mse_loss: out_adj is a row shard {tuple(out_adj.shape)}; the loss is taken on the whole "
+                                  "graph only (rows == columns)")
+    rowptr, col, gval, tshape = _target_csr(target)
+    if tuple(tshape) != tuple(out_adj.shape):
+        raise ValueError(f"adjacency_mse_loss: target is {tuple(tshape)}, out_adj is {tuple(out_adj.shape)}")
+    if gval.device != out_adj.device:
+        raise ValueError(f"adjacency_mse_loss: target is on {gval.device}, out_adj on {out_adj.device}")
+    if isinstance(out_adj, CsrAdjacency):
+        index = (out_adj.rowptr, out_adj.col)
+    else:
+        if out_adj.owner is not None:
+            out_adj.owner.check_ell_bound()
+        index = (out_adj.idx,) if out_adj.layout is None else (out_adj.idx, out_adj.layout)
+    return ops.AdjMseLossFn.run(out_adj.values(), index, (rowptr, col, gval), reduction).reshape(())

@@ -1,5 +1,6 @@
 """Caller-side input pipeline of the small-graph script (SURVEY.md 8b' / 8f rank 4): Planetoid citation graphs and the
-noisy-edge augmentation, as sparse O(E) host code (numpy / scipy; nothing here touches the GPU).
+noisy-edge augmentation, as sparse O(E) host code (numpy / scipy; nothing here touches the GPU), and `remove_interclass_edges`, the
+target of the reference's adjacency supervision, as O(E) tensor code on whatever device the graph is on.
 
 The reference goes through `torch_geometric.datasets.Planetoid(..., transform=NormalizeFeatures())`
 (train_small_graphs.py:339-348) or its own `utils.load_citation` (utils.py:122-196); both read the public
@@ -111,3 +112,16 @@ def add_noisy_edges(rows, cols, N, noise_level, reference_stream=None, seed=0):
     order = np.argsort(key, kind="stable")
     key = key[order]
     return (key // N).astype(np.int32), (key % N).astype(np.int32), np.ones(key.shape[0], np.float32)
+
+
+def remove_interclass_edges(adj, labels):
+    """The supervision target of the reference's adjacency loss (utils.py:1310-1326; train_reddit.py:236): the stored entries of the
+    sparse COO graph `adj` [N,N] (coalesced here) whose two end nodes carry the same label, every kept entry with value 1 whatever
+    `adj` stored there -> coalesced sparse COO float32 [N,N] on adj's device.  labels: [N] integer class per node.  O(E) tensor code
+    on the graph's device; meant to run once, outside the training loop."""
+    import torch
+    a = adj.coalesce()
+    ind = a.indices()
+    labels = torch.as_tensor(labels, device=ind.device)
+    keep = ind[:, labels[ind[0]] == labels[ind[1]]]
+    return torch.sparse_coo_tensor(keep, torch.ones(keep.shape[1], device=ind.device, dtype=torch.float32), a.shape).coalesce()

@@ -251,6 +251,79 @@ def adj_diff_stats(adjacency_arrays, graph_csr, k):
     return out
 
 
+ADJ_LOSS_REDUCTIONS = {"mean": 0, "sum": 1}          # include/dgg_hip_adj_loss.h, DGG_ADJ_LOSS_*
+ADJ_LOSS_CALLS = 0                                   # how often the wrapper has launched the kernel pair
+
+
+def adj_mse_loss(adjacency_arrays, graph_csr, reduction="mean", want_grad=False):
+    """F.mse_loss(A.to_dense(), G.to_dense(), reduction=reduction) of a learned adjacency A [rows,rows] against a target graph G on
+    sparse data (dgg_adj_mse_loss; reference train_reddit.py:236-251) -> (loss float32 [1] on the device, dval or None), on the caller's
+    stream, nothing read back.  adjacency_arrays: (idx int32, w float32) [rows,K] with K <= 64; (idx, w, layout) for chunked rows
+    [chunks,64] (a ChunkLayout; one that is not `wide` is the 64-rank list); or (rowptr_l int64 [rows+1], col_l int32 [E], w [E]) for CSR
+    rows of any width.  A column < 0 marks an empty slot; a row holds each column at most once.  graph_csr: (rowptr int64 [rows+1],
+    col int32 ascending within a row, gval float32, ...).  want_grad: dval (the shape of w) = d loss / d w, exactly 0 at empty slots."""
+    global ADJ_LOSS_CALLS
+    rowptr, col, gval = _chk(graph_csr[0], torch.int64), _chk(graph_csr[1], torch.int32), _chk(graph_csr[2].detach())
+    rows = rowptr.shape[0] - 1
+    assert reduction in ADJ_LOSS_REDUCTIONS, f"adj_mse_loss: reduction {reduction!r} is neither 'mean' nor 'sum'"
+    assert col.shape[0] == gval.shape[0] and rows >= 0
+    if col.shape[0] == 0:                            # (a target without entries: one entry that no row points into)
+        col, gval = col.new_zeros(1), gval.new_zeros(1)
+    idx = lay = rowptr_l = col_l = None
+    if adjacency_arrays[0].dtype == torch.int64:                          # CSR rows
+        rowptr_l, col_l, w = _chk(adjacency_arrays[0], torch.int64), _chk(adjacency_arrays[1], torch.int32), _chk(adjacency_arrays[2].detach())
+        assert rowptr_l.shape[0] == rows + 1 and col_l.shape == w.shape and w.ndim == 1
+        K, chunks = 0, 0
+    else:
+        idx, w = _chk(adjacency_arrays[0], torch.int32), _chk(adjacency_arrays[1].detach())
+        lay = adjacency_arrays[2] if len(adjacency_arrays) > 2 else None
+        lay = lay if (lay is not None and lay.wide) else None
+        assert idx.shape == w.shape and idx.ndim == 2
+        assert (lay.rows == rows and idx.shape[1] == 64) if lay is not None else idx.shape[0] == rows
+        K, chunks = idx.shape[1], (0 if lay is None else idx.shape[0])
+    dev = w.device
+    shape = w.shape
+    if w.numel() == 0 and rows > 0:                  # (an empty tensor has no data pointer: one padding entry that no row points into)
+        if rowptr_l is not None:
+            col_l, w = col_l.new_full((1,), -1), w.new_zeros(1)
+        else:
+            idx, w = idx.new_full((1, K), -1), w.new_zeros((1, K))
+    scale = 1.0 / (float(rows) * float(rows)) if (reduction == "mean" and rows > 0) else 1.0      # (double on the host, one float in the call)
+    out = torch.empty((1,), device=dev, dtype=torch.float32)
+    dval = torch.empty_like(w) if want_grad else None
+    ws = torch.empty((max((rows + 15) // 16, 1),), device=dev, dtype=torch.float64)               # one record per 16 rows
+    ADJ_LOSS_CALLS += 1
+    _lib.check(_lib.lib().dgg_adj_mse_loss(_ptr(idx), _ptr(w), rows, K, None if lay is None else _ptr(_chk(lay.cptr, torch.int32)), chunks,
+                                           _ptr(rowptr_l), _ptr(col_l), _ptr(rowptr), _ptr(col), _ptr(gval), ADJ_LOSS_REDUCTIONS[reduction],
+                                           scale, _ptr(ws), _ptr(dval), _ptr(out), _stream()), "adj_mse_loss")
+    if dval is not None and dval.shape != shape:
+        dval = dval.new_empty(shape)
+    return out, dval
+
+
+class AdjMseLossFn(torch.autograd.Function):
+    """loss [1] = adj_mse_loss over the VALUES of the learned adjacency (index = (idx,), (idx, layout) or (rowptr_l, col_l); the target's
+    values get no gradient).  The forward writes dval = d loss / d values in its one join when a backward will follow (evaluated by
+    run(): inside forward grad mode is always off); the backward is grad_out * dval, with no second launch of the join."""
+
+    @classmethod
+    def run(cls, values, index, graph_csr, reduction="mean"):
+        return cls.apply(values, index, graph_csr, reduction, backward_will_follow(values))
+
+    @staticmethod
+    def forward(ctx, values, index, graph_csr, reduction, want_grad):
+        arrays = (index[0], index[1], values) if index[0].dtype == torch.int64 else (index[0], values) + tuple(index[1:])
+        loss, dval = adj_mse_loss(arrays, graph_csr, reduction, want_grad)
+        ctx.dval = dval
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if ctx.dval is None:
+            raise RuntimeError("AdjMseLossFn: the forward ran without a gradient output (call it through AdjMseLossFn.run)")
+        return grad_out * ctx.dval, None, None, None, None
+
+
 def linear_bwd_multi(x, layers):
     """Weight (and bias) gradients of several layers that share the input x, in ONE pass over x:
     layers = [(W, y or None, dy, act, w_layout, need_db), ...] -> [(dW_s, db_s or None)].  The activation derivative of layer s

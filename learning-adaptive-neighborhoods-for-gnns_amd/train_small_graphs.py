@@ -16,6 +16,7 @@ dgg_amd.ScalarLog (one JSON line per scalar); the evaluation forward stays witho
 the best-validation state in the reference's `save_checkpoint` layout (train_small_graphs.py:210-220: args, epoch,
 model_state_dict, optimizer_state_dict); `--resume FILE` loads `model_state_dict` as its `test_best` does (line 330) -- the
 modules keep the reference's state_dict keys, so files written by either side load in the other.
+`--adj_loss_weight W` adds the reference's supervision of the learned adjacency (train_reddit.py:236-251) to the step, on sparse rows.
 """
 import argparse
 import random
@@ -28,6 +29,7 @@ import torch.nn.functional as F
 from . import data as D
 from . import ops
 from . import model as models
+from .adjacency import CsrAdjacency, EllAdjacency, adjacency_mse_loss
 
 
 def str2bool(v):
@@ -73,6 +75,11 @@ def build_parser():
     p.add_argument("--resume", default=None, help="load model_state_dict from a checkpoint before training")
     p.add_argument("--log_dir", default=None, help="write the reference's training scalars here (values/first_k_*, train_stats/*, histograms)")
     p.add_argument("--dgg_writer_fused", type=str2bool, default=False, help="GCN_DGG: a writer does not leave the fused layer")
+    p.add_argument("--adj_loss_weight", type=float, default=0.0,
+                   help="W > 0: the step minimises nll + W * adjacency_mse_loss(out_adj, remove_interclass_edges(adj, labels)), the "
+                        "reference's supervision of the learned adjacency (train_reddit.py:236-251, W = 10000 there).  The target is cut "
+                        "from the graph AS PASSED to the model (noisy edges included, WITHOUT the self loops the model adds), as the "
+                        "reference cuts it from batch_adj.  Sets dgg_differentiable_adj (GCN_DGG: the separate modules).  0: no change")
     return p
 
 
@@ -107,9 +114,10 @@ def accuracy(out, y):
     return float((out.argmax(1) == y).float().mean())
 
 
-def forward(model, x, adj, **kw):
+def forward(model, x, adj, with_adj=False, **kw):
     """the wrappers differ in what their forward accepts and returns (reference model.py:1236 vs 1368): the script's call
-    (features, adj, edge_index=..., epoch=..., writer=...) is tried first, then without the keywords a wrapper rejects"""
+    (features, adj, edge_index=..., epoch=..., writer=...) is tried first, then without the keywords a wrapper rejects.
+    with_adj: -> (output, out_adj), out_adj None from a wrapper that returns no adjacency"""
     for drop in ((), ("edge_index",), ("edge_index", "epoch", "writer")):
         try:
             out = model(x, adj, **{k: v for k, v in kw.items() if k not in drop})
@@ -117,11 +125,15 @@ def forward(model, x, adj, **kw):
         except TypeError as e:
             if "unexpected keyword" not in str(e):
                 raise
+    if with_adj:
+        return (out[0], out[1] if len(out) > 1 else None) if isinstance(out, tuple) else (out, None)
     return out[0] if isinstance(out, tuple) else out
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.adj_loss_weight > 0.0:
+        args.dgg_differentiable_adj = True     # the loss reaches the generator through the returned adjacency (GCN_DGG: separate modules)
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
@@ -152,13 +164,21 @@ def main(argv=None):
     if args.resume:
         model.load_state_dict(torch.load(args.resume, map_location=device)["model_state_dict"])
     writer = make_writer(args.log_dir) if args.log_dir else None
+    gt_adj = D.remove_interclass_edges(adj, y) if args.adj_loss_weight > 0.0 else None     # once: the same object on every step
     best, bad, t0 = float("inf"), 0, time.time()
     for epoch in range(args.epochs):
         model.train()
         opt.zero_grad()
         with ops.step_zero_pool(device, x.shape[0], 64, max(args.hidden, 64), list(model.parameters())):   # one fill for the step's accumulators
-            out = forward(model, x, adj, edge_index=edge_index, epoch=epoch, writer=writer)
-            loss = F.nll_loss(out[idx["train_idx"]], y[idx["train_idx"]])
+            if gt_adj is None:
+                out = forward(model, x, adj, edge_index=edge_index, epoch=epoch, writer=writer)
+                loss = F.nll_loss(out[idx["train_idx"]], y[idx["train_idx"]])
+            else:
+                out, out_adj = forward(model, x, adj, with_adj=True, edge_index=edge_index, epoch=epoch, writer=writer)
+                if not isinstance(out_adj, (EllAdjacency, CsrAdjacency)):
+                    raise NotImplementedError(f"--adj_loss_weight: {args.model} returns no learned adjacency (got {type(out_adj).__name__})")
+                adj_term = adjacency_mse_loss(out_adj, gt_adj)
+                loss = F.nll_loss(out[idx["train_idx"]], y[idx["train_idx"]]) + args.adj_loss_weight * adj_term
             loss.backward()
         # BEFORE the optimiser step: the learned k must have stayed inside the ELL width and the noise generator must have settled
         # every row -- otherwise this step's adjacency was wrong and its gradients must not reach the weights (one sync per epoch)
@@ -171,6 +191,7 @@ def main(argv=None):
             out = forward(model, x, adj, edge_index=edge_index)
             lv = float(F.nll_loss(out[idx["val_idx"]], y[idx["val_idx"]]))
             print("Epoch:{:04d}".format(epoch + 1), "train", "loss:{:.3f}".format(float(loss)),
+                  *(() if gt_adj is None else ("adj loss:{:.6e}".format(float(adj_term)),)),
                   "| val loss:{:.3f} acc:{:.2f}".format(lv, 100 * accuracy(out[idx["val_idx"]], y[idx["val_idx"]])),
                   "| test acc:{:.2f}".format(100 * accuracy(out[idx["test_idx"]], y[idx["test_idx"]])))
         if lv < best:
