@@ -7,7 +7,9 @@ Public surface mirrors the reference's modules:
     dgg_amd.distributed.{ShardedGCN_DGG, global_nll_loss}                    (GCN_DGG row-sharded across GPUs)
 plus the containers `AllPairs` / `EllAdjacency` / `CsrAdjacency`, the raw kernel wrappers in `dgg_amd.ops` and `ScalarLog`, a
 dependency-free writer for the models' `writer=` argument, and `adjacency_mse_loss`, the reference's supervision of the learned adjacency
-(train_reddit.py:236-251) on sparse rows (target: `dgg_amd.data.remove_interclass_edges`).
+(train_reddit.py:236-251) on sparse rows (target: `dgg_amd.data.remove_interclass_edges`).  Mini-batches of one large graph come
+from `RandomWalkSampler` / `ClusterSampler` (dgg_amd.sampling: the reference's GraphSAINTRandomWalkSampler / ClusterLoader,
+train_large_graphs.py:402-421), each batch a `SubgraphBatch`; `dgg_amd.train_large_graphs` is the harness on top of them.
 """
 from . import _lib, ops  # noqa: F401
 from .adjacency import (AllPairs, CsrAdjacency, EllAdjacency, adjacency_mse_loss, csr_candidates, csr_pattern,  # noqa: F401
@@ -19,3 +21,4 @@ from .model import (DenseGraphConv, DenseGraphConvolution, GAT_DGG_00, GAT_DGG_A
                     GraphConvolution, SAGE_DGG, SAGE_DGG_00)
 from .distributed import ShardedGCN_DGG, global_nll_loss  # noqa: F401
 from .scalar_log import ScalarLog  # noqa: F401
+from .sampling import ClusterSampler, RandomWalkSampler, SubgraphBatch, contiguous_parts  # noqa: F401

@@ -3,7 +3,8 @@ include/dgg_hip.h, the one description of the C ABI (the library's definitions a
 since that ABI version was recorded are declared in include/dgg_hip_next.h (purely additive, folded into dgg_hip.h at the next ABI bump)
 and parsed into tables of their own, NEXT_PROTOTYPES / NEXT_RESTYPES (the header's first block) and NEXT_BLOCKS (one table per later
 block, by the name on its `==== block NAME ====` line): PROTOTYPES stays the recorded ABI.  include/dgg_hip_adj_loss.h (the adjacency
-supervision loss, additive in the same way) is parsed into ADJ_LOSS_PROTOTYPES / ADJ_LOSS_RESTYPES.  Fails loudly when the HIP
+supervision loss, additive in the same way) is parsed into ADJ_LOSS_PROTOTYPES / ADJ_LOSS_RESTYPES, include/dgg_hip_sampling.h (the
+mini-batch sampling entries) into SAMPLING_PROTOTYPES / SAMPLING_RESTYPES.  Fails loudly when the HIP
 library or a header is missing: there is no CPU fallback anywhere in this package."""
 import ctypes as C
 import os
@@ -15,6 +16,7 @@ SO_PATH = os.environ.get("DGG_HIP_SO", os.path.join(_HERE, "libdgg_hip.so"))   #
 HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip.h"))
 NEXT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_next.h"))     # entry points since the recorded ABI
 ADJ_LOSS_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_adj_loss.h"))   # the adjacency supervision loss
+SAMPLING_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_sampling.h"))   # random walks and induced sub-graphs
 
 _C_TYPES = {"int": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float, "size_t": C.c_size_t}
 _C_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
@@ -89,13 +91,20 @@ if set(_ADJ_LOSS_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS)):
     raise DggHipError(f"{ADJ_LOSS_HEADER} declares again what {HEADER} or {NEXT_HEADER} declares: "
                       f"{sorted(set(_ADJ_LOSS_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS)))}")
 
+_SAMPLING_DECLS = _read_header(SAMPLING_HEADER)
+SAMPLING_PROTOTYPES = {name: argtypes for name, (_, argtypes) in _SAMPLING_DECLS.items()}       # ... and for dgg_hip_sampling.h
+SAMPLING_RESTYPES = {name: restype for name, (restype, _) in _SAMPLING_DECLS.items()}
+if set(_SAMPLING_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS) | set(_ADJ_LOSS_DECLS)):
+    raise DggHipError(f"{SAMPLING_HEADER} declares again what {HEADER}, {NEXT_HEADER} or {ADJ_LOSS_HEADER} declares: "
+                      f"{sorted(set(_SAMPLING_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS) | set(_ADJ_LOSS_DECLS)))}")
+
 _lib = None
 
 
 def bind(L, names=None):
-    """Gives the entry points `names` (default: every declared one, of all three headers) of the CDLL handle L the headers' argtypes and
+    """Gives the entry points `names` (default: every declared one, of all four headers) of the CDLL handle L the headers' argtypes and
     restype."""
-    decls = {**_DECLS, **_NEXT_DECLS, **_LATER_DECLS, **_ADJ_LOSS_DECLS}
+    decls = {**_DECLS, **_NEXT_DECLS, **_LATER_DECLS, **_ADJ_LOSS_DECLS, **_SAMPLING_DECLS}
     for name in (decls if names is None else names):
         fn = getattr(L, name)      # AttributeError if the library does not export a declared symbol
         fn.restype, fn.argtypes = decls[name]

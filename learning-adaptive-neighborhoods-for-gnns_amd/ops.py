@@ -324,6 +324,98 @@ class AdjMseLossFn(torch.autograd.Function):
         return grad_out * ctx.dval, None, None, None, None
 
 
+# ---- mini-batch sampling (include/dgg_hip_sampling.h) ---------------------------------------------------------------------------------
+SAMPLING_STATUS = {1: "a node id outside [0, N)", 2: "a CSR row range or column outside the graph"}     # DGG_SAMPLING_BAD_*
+SUBGRAPH_MARK, SUBGRAPH_RELABEL, SUBGRAPH_COUNT, SUBGRAPH_FILL = 0, 1, 2, 3                             # DGG_SUBGRAPH_*
+SUBGRAPH_READBACKS = 0                               # how often induced_subgraph has read (n_b, E_b, status) back: once per call
+
+
+def _graph_csr(rowptr, col, what):
+    rowptr, col = _chk(rowptr, torch.int64), _chk(col, torch.int32)
+    assert rowptr.ndim == 1 and rowptr.shape[0] >= 1 and col.ndim == 1, f"{what}: rowptr int64 [N+1], col int32 [E]"
+    return rowptr, col, rowptr.shape[0] - 1, col.shape[0]
+
+
+def random_walk_nodes(rowptr, col, roots, length, seed, check=False):
+    """The nodes GraphSAINT's random-walk sampler visits (dgg_random_walk_nodes; the law is in include/dgg_hip_sampling.h): CSR graph
+    (rowptr int64 [N+1], col int32 [E]), roots int32 [B], `length` >= 0 steps, seed (s0, s1) -> walk int32 [B, length+1] with
+    walk[:,0] = roots, on the caller's stream.  Nothing is read back: a root outside [0, N) gives a row of -1 (which induced_subgraph
+    refuses); check=True reads the kernel's status word back and raises ValueError on it (one synchronisation: for tests and debugging)."""
+    rowptr, col, N, E = _graph_csr(rowptr, col, "random_walk_nodes")
+    roots = _chk(roots, torch.int32)
+    length = int(length)
+    if roots.ndim != 1:
+        raise ValueError(f"random_walk_nodes: roots must be int32 [B], got shape {tuple(roots.shape)}")
+    if length < 0:
+        raise ValueError(f"random_walk_nodes: length must be >= 0, got {length}")
+    B = roots.shape[0]
+    walk = torch.empty((B, length + 1), device=roots.device, dtype=torch.int32)
+    status = torch.zeros((1,), device=roots.device, dtype=torch.int32)
+    _lib.check(_lib.lib().dgg_random_walk_nodes(_ptr(rowptr), _ptr(col), N, E, _ptr(roots), B, length, int(seed[0]) & 0xffffffff,
+                                                int(seed[1]) & 0xffffffff, _ptr(walk), _ptr(status), _stream()), "random_walk_nodes")
+    if check and int(status) != 0:
+        raise ValueError(f"random_walk_nodes: {SAMPLING_STATUS.get(int(status), int(status))}")
+    return walk
+
+
+class InducedSubgraph:
+    """What induced_subgraph returns: the sub-graph in CSR and COO form with new ids 0..n-1 (ascending original id).
+    orig int32 [n] the original id of every batch node; browptr int64 [n+1], bcol int32 [e] strictly ascending within a row, brow int32
+    [e]; beid int64 [e] the position of every kept entry in the graph's col (gathers values, edge weights, per-edge features);
+    bdeg float32 [n] the row sums of the kept stored values (None without values); newid int32 [N] (-1 outside the set); n, e ints."""
+    __slots__ = ("orig", "browptr", "bcol", "brow", "beid", "bdeg", "newid", "n", "e")
+
+    def __init__(self, **kw):
+        for k_ in self.__slots__:
+            setattr(self, k_, kw[k_])
+
+
+def induced_subgraph(rowptr, col, nodes, values=None):
+    """The sub-graph of the CSR graph (rowptr int64 [N+1], col int32 [E] ascending within a row) induced by `nodes` int32 [M]
+    (duplicates allowed, any order) -> InducedSubgraph, on the caller's stream (dgg_induced_subgraph, phases MARK, RELABEL, COUNT, FILL
+    with two torch.cumsum between them).  values (optional float32 [E]): bdeg = the row sums of the kept values.
+    ONE device read-back per call, (n_b, E_b, status) in one copy after the COUNT phase: the shapes of every output depend on the first
+    two (COUNT runs on min(M, N) rows, an upper bound of n_b, so that n_b itself need not be read before it).  Nothing else is read
+    back.  A node outside [0, N) raises ValueError after that read."""
+    global SUBGRAPH_READBACKS
+    rowptr, col, N, E = _graph_csr(rowptr, col, "induced_subgraph")
+    nodes = _chk(nodes, torch.int32).reshape(-1)
+    dev = rowptr.device
+    if values is not None:
+        values = _chk(values.detach())
+        assert values.shape == col.shape, "induced_subgraph: values must be float32 [E]"
+    M = nodes.shape[0]
+    cap = min(M, N)                                  # an upper bound of the number of distinct nodes
+    i32 = lambda *s: torch.empty(s, device=dev, dtype=torch.int32)  # noqa: E731
+    if cap == 0:                                     # no node asked for, or no node to ask for: nothing is launched, nothing read back
+        return InducedSubgraph(orig=i32(0), browptr=torch.zeros(1, device=dev, dtype=torch.int64), bcol=i32(0), brow=i32(0),
+                               beid=torch.empty(0, device=dev, dtype=torch.int64), bdeg=None if values is None else torch.empty(0, device=dev),
+                               newid=torch.full((N,), -1, device=dev, dtype=torch.int32), n=0, e=0)
+    L, st = _lib.lib(), _stream()
+    status = torch.zeros((1,), device=dev, dtype=torch.int32)
+    flag, newid, orig, bdeg_i = i32(N), i32(N), i32(cap), i32(cap)
+    bdeg = None if values is None else torch.empty((cap,), device=dev, dtype=torch.float32)
+
+    def phase(ph, rank=None, rows=0, browptr=None, e_b=0, out=(None, None, None)):
+        _lib.check(L.dgg_induced_subgraph(ph, _ptr(rowptr), _ptr(col), _ptr(values), N, E, _ptr(nodes), M, _ptr(flag), _ptr(rank), _ptr(newid),
+                                          _ptr(orig), rows, _ptr(bdeg_i), _ptr(bdeg), _ptr(browptr), e_b, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                          _ptr(status), st), "induced_subgraph")
+    phase(SUBGRAPH_MARK)
+    rank = torch.cumsum(flag, 0, dtype=torch.int32)
+    phase(SUBGRAPH_RELABEL, rank, cap)
+    phase(SUBGRAPH_COUNT, rank, cap)
+    browptr = torch.zeros((cap + 1,), device=dev, dtype=torch.int64)
+    torch.cumsum(bdeg_i, 0, dtype=torch.int64, out=browptr[1:])
+    SUBGRAPH_READBACKS += 1
+    n_b, e_b, bad = torch.stack([rank[-1].to(torch.int64), browptr[-1], status[0].to(torch.int64)]).tolist()      # the one read-back
+    if bad:
+        raise ValueError(f"induced_subgraph: {SAMPLING_STATUS.get(bad, bad)} (nodes must lie in [0, {N}))")
+    bcol, brow, beid = i32(e_b), i32(e_b), torch.empty((e_b,), device=dev, dtype=torch.int64)
+    phase(SUBGRAPH_FILL, rank, n_b, browptr, e_b, (bcol, beid, brow))
+    return InducedSubgraph(orig=orig[:n_b], browptr=browptr[:n_b + 1], bcol=bcol, brow=brow, beid=beid, bdeg=None if bdeg is None else bdeg[:n_b],
+                           newid=newid, n=n_b, e=e_b)
+
+
 def linear_bwd_multi(x, layers):
     """Weight (and bias) gradients of several layers that share the input x, in ONE pass over x:
     layers = [(W, y or None, dy, act, w_layout, need_db), ...] -> [(dW_s, db_s or None)].  The activation derivative of layer s
