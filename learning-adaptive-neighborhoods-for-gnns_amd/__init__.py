@@ -9,7 +9,9 @@ plus the containers `AllPairs` / `EllAdjacency` / `CsrAdjacency`, the raw kernel
 dependency-free writer for the models' `writer=` argument, and `adjacency_mse_loss`, the reference's supervision of the learned adjacency
 (train_reddit.py:236-251) on sparse rows (target: `dgg_amd.data.remove_interclass_edges`).  Mini-batches of one large graph come
 from `RandomWalkSampler` / `ClusterSampler` (dgg_amd.sampling: the reference's GraphSAINTRandomWalkSampler / ClusterLoader,
-train_large_graphs.py:402-421), each batch a `SubgraphBatch`; `dgg_amd.train_large_graphs` is the harness on top of them.
+train_large_graphs.py:402-421), each batch a `SubgraphBatch`; `SubgraphBatch.with_noise` gives the `EditedBatch` with the reference's per-batch noisy edges and the
+same-class target of the adjacency loss, built on the device (ops.batch_graph_edit); `dgg_amd.train_large_graphs` is the harness on
+top of them.
 """
 from . import _lib, ops  # noqa: F401
 from .adjacency import (AllPairs, CsrAdjacency, EllAdjacency, adjacency_mse_loss, csr_candidates, csr_pattern,  # noqa: F401
@@ -21,4 +23,4 @@ from .model import (DenseGraphConv, DenseGraphConvolution, GAT_DGG_00, GAT_DGG_A
                     GraphConvolution, SAGE_DGG, SAGE_DGG_00)
 from .distributed import ShardedGCN_DGG, global_nll_loss  # noqa: F401
 from .scalar_log import ScalarLog  # noqa: F401
-from .sampling import ClusterSampler, RandomWalkSampler, SubgraphBatch, contiguous_parts  # noqa: F401
+from .sampling import ClusterSampler, EditedBatch, RandomWalkSampler, SubgraphBatch, contiguous_parts  # noqa: F401

@@ -4,7 +4,8 @@ since that ABI version was recorded are declared in include/dgg_hip_next.h (pure
 and parsed into tables of their own, NEXT_PROTOTYPES / NEXT_RESTYPES (the header's first block) and NEXT_BLOCKS (one table per later
 block, by the name on its `==== block NAME ====` line): PROTOTYPES stays the recorded ABI.  include/dgg_hip_adj_loss.h (the adjacency
 supervision loss, additive in the same way) is parsed into ADJ_LOSS_PROTOTYPES / ADJ_LOSS_RESTYPES, include/dgg_hip_sampling.h (the
-mini-batch sampling entries) into SAMPLING_PROTOTYPES / SAMPLING_RESTYPES.  Fails loudly when the HIP
+mini-batch sampling entries) into SAMPLING_PROTOTYPES / SAMPLING_RESTYPES, include/dgg_hip_batch_graph.h (the batch edit: noisy edges and
+the same-class target) into BATCH_GRAPH_PROTOTYPES / BATCH_GRAPH_RESTYPES.  Fails loudly when the HIP
 library or a header is missing: there is no CPU fallback anywhere in this package."""
 import ctypes as C
 import os
@@ -17,8 +18,9 @@ HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip.h"))
 NEXT_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_next.h"))     # entry points since the recorded ABI
 ADJ_LOSS_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_adj_loss.h"))   # the adjacency supervision loss
 SAMPLING_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_sampling.h"))   # random walks and induced sub-graphs
+BATCH_GRAPH_HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "dgg_hip_batch_graph.h"))   # noisy edges and target of a batch
 
-_C_TYPES = {"int": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float, "size_t": C.c_size_t}
+_C_TYPES = {"int": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float, "size_t": C.c_size_t}
 _C_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
 _INFO = ("dgg_last_error", "dgg_abi_version")    # bound like the rest, not listed in PROTOTYPES
 
@@ -98,13 +100,20 @@ if set(_SAMPLING_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS) | 
     raise DggHipError(f"{SAMPLING_HEADER} declares again what {HEADER}, {NEXT_HEADER} or {ADJ_LOSS_HEADER} declares: "
                       f"{sorted(set(_SAMPLING_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS) | set(_ADJ_LOSS_DECLS)))}")
 
+_BATCH_GRAPH_DECLS = _read_header(BATCH_GRAPH_HEADER)
+BATCH_GRAPH_PROTOTYPES = {name: argtypes for name, (_, argtypes) in _BATCH_GRAPH_DECLS.items()}  # ... and for dgg_hip_batch_graph.h
+BATCH_GRAPH_RESTYPES = {name: restype for name, (restype, _) in _BATCH_GRAPH_DECLS.items()}
+if set(_BATCH_GRAPH_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS) | set(_ADJ_LOSS_DECLS) | set(_SAMPLING_DECLS)):
+    raise DggHipError(f"{BATCH_GRAPH_HEADER} declares again what {HEADER}, {NEXT_HEADER}, {ADJ_LOSS_HEADER} or {SAMPLING_HEADER} declares: "
+                      f"{sorted(set(_BATCH_GRAPH_DECLS) & (set(_DECLS) | set(_NEXT_DECLS) | set(_LATER_DECLS) | set(_ADJ_LOSS_DECLS) | set(_SAMPLING_DECLS)))}")
+
 _lib = None
 
 
 def bind(L, names=None):
-    """Gives the entry points `names` (default: every declared one, of all four headers) of the CDLL handle L the headers' argtypes and
+    """Gives the entry points `names` (default: every declared one, of all five headers) of the CDLL handle L the headers' argtypes and
     restype."""
-    decls = {**_DECLS, **_NEXT_DECLS, **_LATER_DECLS, **_ADJ_LOSS_DECLS, **_SAMPLING_DECLS}
+    decls = {**_DECLS, **_NEXT_DECLS, **_LATER_DECLS, **_ADJ_LOSS_DECLS, **_SAMPLING_DECLS, **_BATCH_GRAPH_DECLS}
     for name in (decls if names is None else names):
         fn = getattr(L, name)      # AttributeError if the library does not export a declared symbol
         fn.restype, fn.argtypes = decls[name]

@@ -219,6 +219,13 @@ def _cached(kind, in_adj, make):
     return out
 
 
+def _seed_cache(kind, in_adj, value):
+    """Enters `value` as what _cached(kind, in_adj, ...) returns for this tensor object and version of its values: for a producer that
+    already holds the converted arrays (a sampler's kernels build the batch graph in CSR form; dgg_amd.sampling.EditedBatch)."""
+    _cached(kind, in_adj, lambda: value)
+    return value
+
+
 def csr_pattern(in_adj):
     """coalesced sparse COO -> (rowptr int64, col int32, erow int32)"""
     def make():

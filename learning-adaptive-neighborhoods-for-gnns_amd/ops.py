@@ -416,6 +416,85 @@ def induced_subgraph(rowptr, col, nodes, values=None):
                            newid=newid, n=n_b, e=e_b)
 
 
+# ---- batch preparation (include/dgg_hip_batch_graph.h) --------------------------------------------------------------------------------
+BATCH_EDIT_STATUS = {1: "a CSR row range or column outside the graph, a row whose columns are not strictly ascending, or prefix sums of "
+                        "another graph"}                                                                   # DGG_BATCH_EDIT_BAD_GRAPH
+BATCH_EDIT_COUNT, BATCH_EDIT_FILL = 0, 1                                                                    # DGG_BATCH_EDIT_*
+BATCH_EDIT_READBACKS = 0                             # how often batch_graph_edit has read (E', E_t, status) back: once per call
+
+
+def noise_threshold(p):
+    """thr of the noise law: min(2^32, int(p * 2^32)) in double, for a probability p in [0, 1]"""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"batch_graph_edit: p must be a probability in [0, 1], got {p}")
+    return min(1 << 32, int(p * 4294967296.0))
+
+
+class EditedBatchGraph:
+    """What batch_graph_edit returns.  The noisy graph (every stored entry plus every noisy pair) in CSR and COO form: nrowptr int64
+    [n+1], ncol int32 [e] strictly ascending within a row, nrow int32 [e], nval float32 [e] (the stored value, 1 for a noisy entry), nsrc
+    int64 [e] (the position of a stored entry in the input's col, -1 for a noisy entry).  The target (the noisy graph's entries between
+    nodes of one label, every value 1): trowptr int64 [n+1], tcol int32 [e_t], trow int32 [e_t], all None without labels.  n, e, e_t ints
+    (e_t = 0 without labels)."""
+    __slots__ = ("nrowptr", "ncol", "nrow", "nval", "nsrc", "trowptr", "tcol", "trow", "n", "e", "e_t")
+
+    def __init__(self, **kw):
+        for k_ in self.__slots__:
+            setattr(self, k_, kw[k_])
+
+
+def batch_graph_edit(rowptr, col, values, p, seed, labels=None):
+    """The noisy edges and the same-class target of a batch graph (dgg_batch_graph_edit; the law is in include/dgg_hip_batch_graph.h):
+    CSR graph (rowptr int64 [n+1], col int32 [E] strictly ascending within a row, values float32 [E]); every off-diagonal pair that is
+    not stored becomes an entry of value 1 with probability p (the reference's 10 * noise_level), a fixed function of seed = (s0, s1);
+    labels (optional, integer [n]): also the target, the entries of the noisy graph whose two nodes carry the same label -> an
+    EditedBatchGraph, on the caller's stream (phases COUNT and FILL with two torch.cumsum between them).  p == 0 gives the graph back
+    (and still builds the target).
+    ONE device read-back per call, (E', E_t, status) in one copy after the COUNT phase.  A broken graph raises ValueError after that
+    read; p outside [0, 1], labels of the wrong length or of a floating dtype raise it before anything is launched."""
+    global BATCH_EDIT_READBACKS
+    rowptr, col, n, E = _graph_csr(rowptr, col, "batch_graph_edit")
+    values = _chk(values.detach())
+    assert values.shape == col.shape, "batch_graph_edit: values must be float32 [E]"
+    thr = noise_threshold(p)
+    dev = rowptr.device
+    if labels is not None:
+        if not torch.is_tensor(labels) or labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.ndim != 1 or labels.shape[0] != n:
+            raise ValueError(f"batch_graph_edit: labels must be an integer tensor [n] = [{n}], got "
+                             f"{(tuple(labels.shape), labels.dtype) if torch.is_tensor(labels) else type(labels).__name__}")
+        labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+    s0, s1 = int(seed[0]) & 0xffffffff, int(seed[1]) & 0xffffffff
+    L, st = _lib.lib(), _stream()
+    i32 = lambda *s: torch.empty(s, device=dev, dtype=torch.int32)  # noqa: E731
+    status = torch.zeros((1,), device=dev, dtype=torch.int32)
+    ndeg, tdeg = i32(n), None if labels is None else i32(n)
+    nrowptr = torch.zeros((n + 1,), device=dev, dtype=torch.int64)
+    trowptr = None if labels is None else torch.zeros((n + 1,), device=dev, dtype=torch.int64)
+
+    def phase(ph, e_n=0, e_t=0, nout=(None, None, None, None), tout=(None, None)):
+        fill = ph == BATCH_EDIT_FILL
+        _lib.check(L.dgg_batch_graph_edit(ph, _ptr(rowptr), _ptr(col), _ptr(values), n, E, _ptr(labels), s0, s1, thr, _ptr(ndeg), _ptr(tdeg),
+                                          _ptr(nrowptr) if fill else None, e_n, _ptr(nout[0]), _ptr(nout[1]), _ptr(nout[2]), _ptr(nout[3]),
+                                          _ptr(trowptr) if fill else None, e_t, _ptr(tout[0]), _ptr(tout[1]), _ptr(status), st), "batch_graph_edit")
+    phase(BATCH_EDIT_COUNT)
+    if n > 0:
+        torch.cumsum(ndeg, 0, dtype=torch.int64, out=nrowptr[1:])
+        if labels is not None:
+            torch.cumsum(tdeg, 0, dtype=torch.int64, out=trowptr[1:])
+    BATCH_EDIT_READBACKS += 1
+    e_n, e_t, bad = torch.stack([nrowptr[-1], nrowptr[-1] if labels is None else trowptr[-1], status[0].to(torch.int64)]).tolist()   # the one read-back
+    if bad:
+        raise ValueError(f"batch_graph_edit: {BATCH_EDIT_STATUS.get(bad, bad)}")
+    if labels is None:
+        e_t = 0
+    nout = (i32(e_n), i32(e_n), torch.empty((e_n,), device=dev, dtype=torch.float32), torch.empty((e_n,), device=dev, dtype=torch.int64))
+    tout = (None, None) if labels is None else (i32(e_t), i32(e_t))
+    phase(BATCH_EDIT_FILL, e_n, e_t, nout, tout)
+    return EditedBatchGraph(nrowptr=nrowptr, ncol=nout[0], nrow=nout[1], nval=nout[2], nsrc=nout[3], trowptr=trowptr, tcol=tout[0], trow=tout[1],
+                            n=n, e=e_n, e_t=e_t)
+
+
 def linear_bwd_multi(x, layers):
     """Weight (and bias) gradients of several layers that share the input x, in ONE pass over x:
     layers = [(W, y or None, dy, act, w_layout, need_db), ...] -> [(dW_s, db_s or None)].  The activation derivative of layer s

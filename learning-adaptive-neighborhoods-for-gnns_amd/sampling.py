@@ -15,13 +15,23 @@ its per-object cache.  A batch costs one kernel for the walks, a clear and four 
 them, the gathers that dress the result as a sparse tensor, and ONE device read-back (the batch's node and edge counts: its tensors'
 shapes).
 
+    edited = batch.with_noise(noise_level, loader.noise_seed(batch.step), labels=y_b)     # add_noisy_edges + remove_interclass_edges
+    output, out_adj, _ = model(x_b, edited.adj);  adjacency_mse_loss(out_adj, edited.target)
+
+with_noise is the reference's per-batch edit (train_large_graphs.py:230-236) on the device (ops.batch_graph_edit,
+include/dgg_hip_batch_graph.h): two kernels, two torch.cumsum and ONE more read-back (the edited graphs' entry counts).  Its noise is
+a counter-based law keyed by noise_seed(step), a fixed function of (seed, epoch, step): every batch gets its own noise, where the
+reference re-seeds numpy to 0 for every batch, and the realisation is that law's, not numpy's stream.
+
 Not built (the reference loop never reads them, or the data is not available): GraphSAINT's node_norm / edge_norm coverage estimates
 (sample_coverage), METIS partitioning (ClusterData) -- `parts` is the caller's, contiguous_parts is a stand-in that is NOT METIS --
 and num_workers (the sampling runs on the device, on the caller's stream)."""
 import torch
 
 from . import ops
-from .adjacency import _cached, csr_pattern
+from .adjacency import CsrAdjacency, _cached, _seed_cache, csr_pattern
+
+NOISE_STREAM = 0x6E6F6973          # folded into s1 by noise_seed: the noise of a step is not the stream its walks used
 
 
 class SubgraphBatch:
@@ -30,10 +40,11 @@ class SubgraphBatch:
     adj sparse COO float32 [n, n], coalesced by construction (sorted unique indices), values = the graph's stored values: what the
     models take as in_adj; edge_index int64 [2, e] = adj.indices(); eid int64 [e] the position of every batch edge among the graph's
     coalesced entries (gathers edge weights or per-edge features: w[eid]); sub: the ops.InducedSubgraph it was built from (CSR arrays,
-    bdeg = the prior degrees csr_candidates would compute for adj)."""
+    bdeg = the prior degrees csr_candidates would compute for adj); step: the batch's number in its epoch (None when built by hand)."""
 
-    def __init__(self, sub, values):
+    def __init__(self, sub, values, step=None):
         self.sub = sub
+        self.step = step
         self.nodes = sub.orig.long()
         self.eid = sub.beid
         self.edge_index = torch.stack([sub.brow.long(), sub.bcol.long()])
@@ -42,6 +53,49 @@ class SubgraphBatch:
 
     def take(self, t):
         """t[nodes]: the batch's rows of a per-node tensor of the whole graph (features, labels, masks)"""
+        return t[self.nodes]
+
+    def with_noise(self, noise_level, seed, labels=None):
+        """The batch with the reference's noisy edges, and the supervision target of its adjacency loss when `labels` (integer [n], the
+        batch nodes' classes) are given -> EditedBatch.  Each off-diagonal pair that is not an edge becomes one of value 1 with
+        probability 10 * noise_level (the reference's factor, utils.py:93; clipped to [0, 1]), a fixed function of seed = (s0, s1): a
+        sampler's noise_seed(batch.step).  On the device, on the caller's stream, one read-back (ops.batch_graph_edit)."""
+        p = min(max(10.0 * float(noise_level), 0.0), 1.0)
+        return EditedBatch(self, ops.batch_graph_edit(self.sub.browptr, self.sub.bcol, self.adj._values(), p, seed, labels))
+
+
+class EditedBatch:
+    """A SubgraphBatch after with_noise.  nodes, take, num_nodes, step as there; num_edges counts the noisy entries too.
+    adj sparse COO float32 [n, n], coalesced by construction: the batch's stored entries with their values plus the noisy entries with
+    value 1; edge_index int64 [2, e] = adj.indices(); is_noise bool [e]; eid int64 [e]: the position of a stored entry among the whole
+    graph's coalesced entries (the source batch's eid), -1 for a noisy entry; target: the CsrAdjacency of the entries of adj between
+    nodes of one label, every value 1 (remove_interclass_edges(adj, labels); adjacency_mse_loss takes it as it is), None without
+    labels; edit: the ops.EditedBatchGraph.
+    csr_pattern(adj) and csr_candidates(adj) (and the float32 values) are seeded with the kernel's own CSR arrays: the first use of adj
+    coalesces and converts nothing."""
+
+    def __init__(self, batch, edit):
+        self.source, self.edit = batch, edit
+        self.nodes, self.step = batch.nodes, batch.step
+        self.num_nodes, self.num_edges = edit.n, edit.e
+        self.edge_index = torch.stack([edit.nrow.long(), edit.ncol.long()])
+        self.adj = torch.sparse_coo_tensor(self.edge_index, edit.nval, (edit.n, edit.n), is_coalesced=True)
+        self.is_noise = edit.nsrc < 0
+        if batch.eid.shape[0] == 0:                    # (nothing to gather from: every entry is noise)
+            self.eid = torch.full_like(edit.nsrc, -1)
+        else:
+            self.eid = torch.where(self.is_noise, edit.nsrc, batch.eid[edit.nsrc.clamp(min=0)])
+        self.target = None
+        if edit.trowptr is not None:
+            self.target = CsrAdjacency(edit.trowptr, edit.tcol, edit.trow, torch.ones(edit.e_t, device=edit.nval.device), edit.n)
+        # row sums as csr_candidates forms them: differences of a float64 running sum (deterministic)
+        cs = torch.cat([edit.nval.new_zeros(1, dtype=torch.float64), edit.nval.double().cumsum(0)])
+        deg = (cs[edit.nrowptr[1:]] - cs[edit.nrowptr[:-1]]).float()
+        _seed_cache("pattern", self.adj, (edit.nrowptr, edit.ncol, edit.nrow))
+        _seed_cache("candidates", self.adj, (edit.nrowptr, edit.ncol, deg))
+        _seed_cache("values_f32", self.adj, edit.nval)
+
+    def take(self, t):
         return t[self.nodes]
 
 
@@ -98,10 +152,15 @@ class RandomWalkSampler:
         """the (s0, s1) of the step's walks"""
         return self.seed & 0xffffffff, (self.epoch * 0x10001 + step) & 0xffffffff
 
+    def noise_seed(self, step):
+        """the (s0, s1) of the step's noisy edges (SubgraphBatch.with_noise): a fixed function of (seed, epoch, step), another stream
+        than walk_seed's"""
+        return self.seed & 0xffffffff, ((self.epoch * 0x10001 + step) ^ NOISE_STREAM) & 0xffffffff
+
     def batch(self, step):
         walk = ops.random_walk_nodes(self.rowptr, self.col, self.roots(step).to(self.rowptr.device), self.walk_length, self.walk_seed(step))
         # the node set is the walk's unique nodes: duplicates are left to the mark phase of the cut
-        return SubgraphBatch(ops.induced_subgraph(self.rowptr, self.col, walk.reshape(-1), self.values), self.values)
+        return SubgraphBatch(ops.induced_subgraph(self.rowptr, self.col, walk.reshape(-1), self.values), self.values, step=step)
 
     def __iter__(self):
         return (self.batch(step) for step in range(self.num_steps))
@@ -151,12 +210,16 @@ class ClusterSampler:
             return list(range(self.num_clusters))
         return torch.randperm(self.num_clusters, generator=_generator(self.seed, self.epoch)).tolist()
 
+    def noise_seed(self, step):
+        """the (s0, s1) of the noisy edges of the epoch's batch number `step` (by position in the epoch): RandomWalkSampler's function"""
+        return self.seed & 0xffffffff, ((self.epoch * 0x10001 + step) ^ NOISE_STREAM) & 0xffffffff
+
     def batch_nodes(self, clusters):
         """int32 [M] on the graph's device: the members of the given clusters (slices of one device array: nothing is read back)"""
         return torch.cat([self.order[self.offsets[c]:self.offsets[c + 1]] for c in clusters])
 
     def __iter__(self):
         order = self.cluster_order()
-        for s in range(0, self.num_clusters, self.batch_size):
+        for step, s in enumerate(range(0, self.num_clusters, self.batch_size)):
             nodes = self.batch_nodes(order[s:s + self.batch_size])
-            yield SubgraphBatch(ops.induced_subgraph(self.rowptr, self.col, nodes, self.values), self.values)
+            yield SubgraphBatch(ops.induced_subgraph(self.rowptr, self.col, nodes, self.values), self.values, step=step)

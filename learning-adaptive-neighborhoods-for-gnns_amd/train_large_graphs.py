@@ -15,7 +15,8 @@ Flags follow the reference script where it has them (--dataloader, --graphsaint_
 --epochs, --seed, --data) and train_small_graphs.py for everything the model constructors read (its parser is the base of this one).
 New here, because the reference hard-codes them: --num_steps (GraphSAINT's num_steps=5), --cluster_parts / --cluster_bs (ClusterData's
 num_parts=500, ClusterLoader's batch_size=5), --adj_loss_weight (the reference's constant 10000 is the default; 0 drops the term and
-with it dgg_differentiable_adj, so the model stays on its fused layer).
+with it dgg_differentiable_adj, so the model stays on its fused layer), --batch_noise {host,device} (where a training batch gets its
+noisy edges and its target; below).
 
 What differs from the reference loop, deliberately:
   * the clusters are dgg_amd.sampling.contiguous_parts, NOT a METIS partition (not available);
@@ -24,7 +25,16 @@ What differs from the reference loop, deliberately:
   * check_ell_bound() runs before every optimiser step, as in train_small_graphs.py;
   * evaluation runs on the WHOLE graph (the public validation / test split), once per epoch, as the reference's `test` covers it;
   * noisy edges (--edge_noise_level > 0) are added per batch on the host, as the reference does (add_noisy_edges on the batch's
-    scipy matrix): one extra device -> host copy of the batch's edge list per step.  0 keeps the step on the device."""
+    scipy matrix): one extra device -> host copy of the batch's edge list per step.  0 keeps the step on the device.
+
+--batch_noise device (the default, host, is the path above, unchanged): one batch.with_noise(edge_noise_level, loader.noise_seed(step),
+labels) replaces both add_noisy_edges and remove_interclass_edges for the TRAINING batches (ops.batch_graph_edit,
+include/dgg_hip_batch_graph.h).  No .cpu() call and no numpy work stays on the step: a batch costs two read-backs, one for the cut
+and one for the edit.  The whole-graph evaluation adjacency stays on the host path.  Two deliberate deviations from the reference:
+  * every batch gets its OWN noise, a fixed function of (seed, epoch, step); the reference's add_noisy_edges re-seeds numpy to 0 on
+    every call, so every batch there gets the top-left corner of one and the same noise matrix;
+  * the realisation is the header's counter-based law (each absent off-diagonal pair independently, with probability
+    10 * edge_noise_level), not numpy's stream -- the trade data.add_noisy_edges(reference_stream=False) already makes."""
 import random
 import time
 
@@ -49,6 +59,9 @@ def build_parser():
     p.add_argument("--num_steps", type=int, default=5, help="batches per epoch of the SAINT loader (hard-coded 5 in the reference)")
     p.add_argument("--cluster_parts", type=int, default=500, help="number of clusters (ClusterData num_parts; contiguous runs of ids, not METIS)")
     p.add_argument("--cluster_bs", type=int, default=5, help="clusters per batch (ClusterLoader batch_size)")
+    p.add_argument("--batch_noise", default="host", choices=["host", "device"],
+                   help="where a training batch gets its noisy edges and its same-class target: host (numpy + torch, as the reference) or "
+                        "device (one kernel pair, SubgraphBatch.with_noise)")
     p.add_argument("--print_batches", type=S.str2bool, default=False, help="one line per training batch (nodes, edges, nll, adjacency term)")
     return p
 
@@ -80,22 +93,27 @@ def train_gcn_dgg(args, model, opt, loader, x, y, train_mask, epoch, writer=None
     terms = []
     for step, batch in enumerate(loader):
         x_b, y_b, mask = batch.take(x), batch.take(y), batch.take(train_mask)
-        batch_adj = noisy_batch_adj(batch, args.edge_noise_level)
+        edited = None
+        if args.batch_noise == "device":
+            edited = batch.with_noise(args.edge_noise_level, loader.noise_seed(step), labels=y_b if W > 0.0 else None)
+            batch_adj, edge_index = edited.adj, edited.edge_index
+        else:
+            batch_adj, edge_index = noisy_batch_adj(batch, args.edge_noise_level), batch.edge_index
         num_nodes = int(mask.sum())
         if num_nodes == 0 and W <= 0.0:
             continue                                   # nothing to learn from: no training node and no adjacency term
         opt.zero_grad()
         with ops.step_zero_pool(x.device, batch.num_nodes, 64, max(args.hidden, 64), list(model.parameters())):
             if W > 0.0:
-                gt = D.remove_interclass_edges(batch_adj, y_b)
-                out, out_adj = S.forward(model, x_b, batch_adj, with_adj=True, edge_index=batch.edge_index, epoch=epoch, writer=writer)
+                gt = D.remove_interclass_edges(batch_adj, y_b) if edited is None else edited.target
+                out, out_adj = S.forward(model, x_b, batch_adj, with_adj=True, edge_index=edge_index, epoch=epoch, writer=writer)
                 if not isinstance(out_adj, (EllAdjacency, CsrAdjacency)):
                     raise NotImplementedError(f"--adj_loss_weight: {args.model} returns no learned adjacency (got {type(out_adj).__name__})")
                 adj_term = adjacency_mse_loss(out_adj, gt)
                 loss = W * adj_term if num_nodes == 0 else F.nll_loss(out[mask], y_b[mask]) + W * adj_term
             else:
                 adj_term = None
-                out = S.forward(model, x_b, batch_adj, edge_index=batch.edge_index, epoch=epoch, writer=writer)
+                out = S.forward(model, x_b, batch_adj, edge_index=edge_index, epoch=epoch, writer=writer)
                 loss = F.nll_loss(out[mask], y_b[mask])
             loss.backward()
         for dg in getattr(model, "dggs", []):          # BEFORE the optimiser step, as train_small_graphs.py does
